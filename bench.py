@@ -4,7 +4,11 @@
 `python bench.py --gpus N --steps K --warmup W` runs the BASELINE.json
 headline config — ViT-L/16 DINOv3 pretrain @224px, batch 64/GPU, bf16,
 synthetic data, random-init weights — and prints ONE JSON line from rank 0
-with the whole-job images/sec.
+with the whole-job images/sec. A plain run does only that: set up, warm up,
+time the K steps, print the line. `--dump-outputs DIR` additionally writes the
+last timed step's results as .npy files (inputs are seeded, so two builds can
+be compared output for output); `--full` is where any measurement beyond the
+headline figure belongs (there is none today).
 
 For N>1 the driver launches via torch.distributed.run (one rank per GPU over
 RCCL); RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* come from the env.
@@ -15,8 +19,11 @@ from __future__ import annotations
 import argparse
 import json
 import os
+import random
 import sys
 import time
+
+import numpy as np
 import torch
 
 REPO_ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -60,6 +67,14 @@ def parse_args():
     p.add_argument("--num-workers", type=int, default=12,
                    help="dataloader workers per rank for --data loader")
     p.add_argument("--profile-tag", type=str, default="", help="label kernels for rocprof runs")
+    p.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                   help="after the timed steps, write what the last timed step "
+                        "returned (loss, loss terms) and a fixed sample of the "
+                        "parameters it updated as DIR/<name>.npy (float32)")
+    p.add_argument("--full", action="store_true",
+                   help="also run the measurements beyond the headline figure "
+                        "(none at present: a plain run already does only the "
+                        "timed steps)")
     return p.parse_args()
 
 
@@ -112,6 +127,25 @@ def make_synthetic_batch(cfg, device, dtype, n_batches=4):
     return batches
 
 
+_DUMP_ELEMS_PER_PARAM = 1024
+
+
+def dump_outputs(out_dir, last_out, model):
+    """Write the last timed step's results as <out_dir>/<name>.npy (float32):
+    the loss and loss terms the step returned, plus the leading
+    _DUMP_ELEMS_PER_PARAM elements of every student / teacher parameter after
+    the step's optimizer and EMA updates (a fixed sample, a few MB)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {name: t.float().cpu().numpy() for name, t in last_out.items()}
+    for tower in ("student", "teacher"):
+        parts = [p.detach().reshape(-1)[:_DUMP_ELEMS_PER_PARAM].float().cpu()
+                 for name, p in model.named_parameters() if name.startswith(tower + "_")]
+        if parts:
+            arrays[f"{tower}_params_sample"] = torch.cat(parts).numpy()
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(arr, dtype=np.float32))
+
+
 def main():
     args = parse_args()
     os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
@@ -128,7 +162,11 @@ def main():
     if use_gpu:
         torch.cuda.set_device(device)
 
+    # the mask generator and collate draw from `random` and numpy: seed all
+    # three so the same arguments give the same inputs run to run
     torch.manual_seed(1234 + rank)
+    random.seed(1234 + rank)
+    np.random.seed(1234 + rank)
     cfg = build_cfg(args)
     dtype = DTYPE_MAP[args.dtype] if use_gpu else torch.float32
 
@@ -186,9 +224,15 @@ def main():
             return batches[i % len(batches)]
     clip = cfg.optim.clip_grad
 
-    def step(i):
+    last_out = {}
+
+    def step(i, keep=False):
         data = next_batch(i)
-        loss, _ = model(data, teacher_temp=0.07, iteration=i)
+        loss, metrics = model(data, teacher_temp=0.07, iteration=i)
+        if keep:
+            last_out["loss"] = loss.detach()
+            last_out.update({k: v.detach() for k, v in metrics.items()
+                             if isinstance(v, torch.Tensor)})
         loss.backward()
         finalize_backward()
         clip_scales = None
@@ -212,9 +256,10 @@ def main():
     parallel.barrier()
     if use_gpu:
         torch.cuda.synchronize()
+    dump_last = bool(args.dump_outputs)
     t0 = time.perf_counter()
     for i in range(args.steps):
-        step(args.warmup + i)
+        step(args.warmup + i, keep=dump_last and i == args.steps - 1)
     parallel.barrier()
     if use_gpu:
         torch.cuda.synchronize()
@@ -235,6 +280,9 @@ def main():
         peak_gb = torch.cuda.max_memory_allocated(device) / 2**30
         print(f"[bench] peak memory allocated: {peak_gb:.1f} GiB "
               f"(rank {rank}, 288 GiB HBM3E)", file=sys.stderr)
+
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last_out, model)
 
     if rank == 0:
         parallelism = ("fsdp" if (world > 1 and cfg.compute_precision.sharding_strategy

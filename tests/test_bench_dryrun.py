@@ -37,6 +37,10 @@ def test_bench_torchrun_cpu_world8():
     env = dict(os.environ)
     env.pop("RANK", None)
     env.pop("WORLD_SIZE", None)
+    # the rehearsal is CPU/gloo by design: on a machine with fewer than 8
+    # GPUs the ranks must not pick the nccl backend and a device per rank
+    env["HIP_VISIBLE_DEVICES"] = "-1"
+    env["CUDA_VISIBLE_DEVICES"] = "-1"
     proc = subprocess.run(cmd, cwd=REPO_ROOT, env=env, capture_output=True,
                           text=True, timeout=520)
     assert proc.returncode == 0, f"stdout:\n{proc.stdout[-2000:]}\nstderr:\n{proc.stderr[-3000:]}"
