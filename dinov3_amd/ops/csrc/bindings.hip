@@ -8,6 +8,8 @@
 
 #include <vector>
 
+#include "common.h"  // COLRED_MAX_PARTIALS
+
 #define CHECK_INPUT(x) \
   TORCH_CHECK(x.is_cuda() && x.is_contiguous(), #x " must be a contiguous HIP tensor")
 
@@ -17,12 +19,12 @@ void launch_layernorm_fwd(const T*, const T*, const T*, T*, float*, float*, long
                           float, hipStream_t);
 template <typename T>
 void launch_layernorm_bwd(const T*, const T*, const T*, const float*, const float*, T*,
-                          float*, float*, long, int, hipStream_t);
+                          float*, T*, T*, long, int, hipStream_t);
 template <typename T>
 void launch_rmsnorm_fwd(const T*, const T*, T*, float*, long, int, float, hipStream_t);
 template <typename T>
-void launch_rmsnorm_bwd(const T*, const T*, const T*, const float*, T*, float*, long, int,
-                        hipStream_t);
+void launch_rmsnorm_bwd(const T*, const T*, const T*, const float*, T*, float*, T*, long,
+                        int, hipStream_t);
 template <typename T>
 void launch_l2norm_fwd(const T*, T*, float*, long, int, float, hipStream_t);
 template <typename T>
@@ -30,23 +32,25 @@ void launch_l2norm_bwd(const T*, const T*, const float*, T*, long, int, float, h
 template <typename T>
 void launch_bias_gelu_fwd(const T*, const T*, T*, long, int, hipStream_t);
 template <typename T>
-void launch_bias_gelu_bwd(const T*, const T*, const T*, T*, float*, long, int, hipStream_t);
+void launch_bias_gelu_bwd(const T*, const T*, const T*, T*, float*, T*, long, int,
+                          hipStream_t);
 template <typename T>
 void launch_ls_axpy_fwd(const T*, const T*, const T*, T*, long, int, hipStream_t);
 template <typename T>
-void launch_ls_axpy_bwd(const T*, const T*, const T*, T*, float*, long, int, hipStream_t);
+void launch_ls_axpy_bwd(const T*, const T*, const T*, T*, float*, T*, long, int,
+                        hipStream_t);
 template <typename T>
 void launch_ls_axpy_bias_fwd(const T*, const T*, const T*, const T*, T*, long, int,
                              hipStream_t);
 template <typename T>
-void launch_ls_axpy_bias_bwd(const T*, const T*, const T*, const T*, T*, float*, float*,
+void launch_ls_axpy_bias_bwd(const T*, const T*, const T*, const T*, T*, float*, T*, T*,
                              long, int, hipStream_t);
 template <typename T>
 void launch_ls_scatter_add(T*, const long*, const T*, const T*, const T*, const float*,
                            long, int, hipStream_t);
 template <typename T>
 void launch_ls_scatter_bwd(const T*, const long*, const T*, const T*, const T*,
-                           const float*, T*, float*, float*, long, int, hipStream_t);
+                           const float*, T*, float*, T*, T*, long, int, hipStream_t);
 template <typename T>
 void launch_row_gather(const T*, const long*, T*, long, int, hipStream_t);
 template <typename T>
@@ -160,6 +164,14 @@ hipStream_t current_stream() { return at::hip::getCurrentHIPStream().stream(); }
     }                                                                          \
   }()
 
+// fp32 workspace of the two-stage column reduction (common.h): one row of D
+// per block for each of `n_acc` parameter gradients. Uninitialised on purpose:
+// the kernels write every row they later read.
+torch::Tensor colreduce_workspace(int n_acc, int D, const torch::Tensor& like) {
+  return torch::empty({(long)n_acc * COLRED_MAX_PARTIALS, D},
+                      like.options().dtype(torch::kFloat));
+}
+
 // ------------------------------- norms ---------------------------------
 
 std::vector<torch::Tensor> layernorm_fwd(torch::Tensor x, torch::Tensor w, torch::Tensor b,
@@ -187,18 +199,17 @@ std::vector<torch::Tensor> layernorm_bwd(torch::Tensor dy, torch::Tensor x, torc
   const int D = x.size(-1);
   const long rows = x.numel() / D;
   auto dx = torch::empty_like(x);
-  // 8 shadow accumulators (LN_SHADOWS in norms.hip): per-address atomic
-  // chains shrink 8x; the [8, D] partials are summed here
-  auto dw = torch::zeros({32, D}, x.options().dtype(torch::kFloat));
-  auto db = torch::zeros({32, D}, x.options().dtype(torch::kFloat));
+  auto dw = torch::empty({D}, x.options());
+  auto db = torch::empty({D}, x.options());
+  auto ws = colreduce_workspace(2, D, x);
   DISPATCH_FLOAT_BF16(x.scalar_type(), "layernorm_bwd", [&] {
     launch_layernorm_bwd<scalar_t>(
         (const scalar_t*)dy.data_ptr(), (const scalar_t*)x.data_ptr(),
         (const scalar_t*)w.data_ptr(), mean.data_ptr<float>(), rstd.data_ptr<float>(),
-        (scalar_t*)dx.data_ptr(), dw.data_ptr<float>(), db.data_ptr<float>(), rows, D,
-        current_stream());
+        (scalar_t*)dx.data_ptr(), ws.data_ptr<float>(), (scalar_t*)dw.data_ptr(),
+        (scalar_t*)db.data_ptr(), rows, D, current_stream());
   });
-  return {dx, dw.sum(0).to(x.scalar_type()), db.sum(0).to(x.scalar_type())};
+  return {dx, dw, db};
 }
 
 std::vector<torch::Tensor> rmsnorm_fwd(torch::Tensor x, torch::Tensor w, double eps) {
@@ -221,14 +232,15 @@ std::vector<torch::Tensor> rmsnorm_bwd(torch::Tensor dy, torch::Tensor x, torch:
   const int D = x.size(-1);
   const long rows = x.numel() / D;
   auto dx = torch::empty_like(x);
-  auto dw = torch::zeros({D}, x.options().dtype(torch::kFloat));
+  auto dw = torch::empty({D}, x.options());
+  auto ws = colreduce_workspace(1, D, x);
   DISPATCH_FLOAT_BF16(x.scalar_type(), "rmsnorm_bwd", [&] {
     launch_rmsnorm_bwd<scalar_t>((const scalar_t*)dy.data_ptr(), (const scalar_t*)x.data_ptr(),
                                  (const scalar_t*)w.data_ptr(), rstd.data_ptr<float>(),
-                                 (scalar_t*)dx.data_ptr(), dw.data_ptr<float>(), rows, D,
-                                 current_stream());
+                                 (scalar_t*)dx.data_ptr(), ws.data_ptr<float>(),
+                                 (scalar_t*)dw.data_ptr(), rows, D, current_stream());
   });
-  return {dx, dw.to(x.scalar_type())};
+  return {dx, dw};
 }
 
 std::vector<torch::Tensor> l2norm_fwd(torch::Tensor x, double eps) {
@@ -279,14 +291,16 @@ std::vector<torch::Tensor> bias_gelu_bwd(torch::Tensor dy, torch::Tensor x,
   const int H = x.size(-1);
   const long rows = x.numel() / H;
   auto dx = torch::empty_like(x);
-  auto dbias = torch::zeros({32, H}, x.options().dtype(torch::kFloat));
+  auto dbias = torch::empty({H}, x.options());
+  auto ws = colreduce_workspace(1, H, x);
   DISPATCH_FLOAT_BF16(x.scalar_type(), "bias_gelu_bwd", [&] {
     launch_bias_gelu_bwd<scalar_t>((const scalar_t*)dy.data_ptr(),
                                    (const scalar_t*)x.data_ptr(),
                                    (const scalar_t*)bias.data_ptr(), (scalar_t*)dx.data_ptr(),
-                                   dbias.data_ptr<float>(), rows, H, current_stream());
+                                   ws.data_ptr<float>(), (scalar_t*)dbias.data_ptr(), rows, H,
+                                   current_stream());
   });
-  return {dx, dbias.sum(0).to(x.scalar_type())};
+  return {dx, dbias};
 }
 
 torch::Tensor ls_axpy_fwd(torch::Tensor x, torch::Tensor res, torch::Tensor gamma) {
@@ -328,15 +342,16 @@ std::vector<torch::Tensor> ls_axpy_bwd(torch::Tensor dout, torch::Tensor res,
   const int D = dout.size(-1);
   const long rows = dout.numel() / D;
   auto dres = torch::empty_like(dout);
-  auto dgamma = torch::zeros({32, D}, dout.options().dtype(torch::kFloat));
+  auto dgamma = torch::empty({D}, dout.options());
+  auto ws = colreduce_workspace(1, D, dout);
   DISPATCH_FLOAT_BF16(dout.scalar_type(), "ls_axpy_bwd", [&] {
     launch_ls_axpy_bwd<scalar_t>((const scalar_t*)dout.data_ptr(),
                                  (const scalar_t*)res.data_ptr(),
                                  (const scalar_t*)gamma.data_ptr(),
-                                 (scalar_t*)dres.data_ptr(), dgamma.data_ptr<float>(),
-                                 rows, D, current_stream());
+                                 (scalar_t*)dres.data_ptr(), ws.data_ptr<float>(),
+                                 (scalar_t*)dgamma.data_ptr(), rows, D, current_stream());
   });
-  return {dres, dgamma.sum(0).to(dout.scalar_type())};
+  return {dres, dgamma};
 }
 
 std::vector<torch::Tensor> ls_axpy_bias_bwd(torch::Tensor dout, torch::Tensor res,
@@ -345,17 +360,17 @@ std::vector<torch::Tensor> ls_axpy_bias_bwd(torch::Tensor dout, torch::Tensor re
   const int D = dout.size(-1);
   const long rows = dout.numel() / D;
   auto dres = torch::empty_like(dout);
-  auto fopt = dout.options().dtype(torch::kFloat);
-  auto dgamma = torch::zeros({32, D}, fopt);
-  auto dbias = torch::zeros({32, D}, fopt);
+  auto dgamma = torch::empty({D}, dout.options());
+  auto dbias = torch::empty({D}, dout.options());
+  auto ws = colreduce_workspace(2, D, dout);
   DISPATCH_FLOAT_BF16(dout.scalar_type(), "ls_axpy_bias_bwd", [&] {
     launch_ls_axpy_bias_bwd<scalar_t>(
         (const scalar_t*)dout.data_ptr(), (const scalar_t*)res.data_ptr(),
         (const scalar_t*)gamma.data_ptr(), (const scalar_t*)bias.data_ptr(),
-        (scalar_t*)dres.data_ptr(), dgamma.data_ptr<float>(), dbias.data_ptr<float>(),
-        rows, D, current_stream());
+        (scalar_t*)dres.data_ptr(), ws.data_ptr<float>(), (scalar_t*)dgamma.data_ptr(),
+        (scalar_t*)dbias.data_ptr(), rows, D, current_stream());
   });
-  return {dres, dgamma.sum(0).to(dout.scalar_type()), dbias.sum(0).to(dout.scalar_type())};
+  return {dres, dgamma, dbias};
 }
 
 torch::Tensor row_gather(torch::Tensor src, torch::Tensor idx) {
@@ -424,9 +439,9 @@ std::vector<torch::Tensor> ls_scatter_bwd(torch::Tensor dy, torch::Tensor idx,
   const int D = dy.size(-1);
   const long M = idx.numel();
   auto dres = torch::empty_like(src);
-  auto fopt = dy.options().dtype(torch::kFloat);
-  auto dgamma = gamma.defined() ? torch::zeros({32, D}, fopt) : torch::Tensor();
-  auto dbias = bias.defined() ? torch::zeros({32, D}, fopt) : torch::Tensor();
+  auto dgamma = gamma.defined() ? torch::empty({D}, dy.options()) : torch::Tensor();
+  auto dbias = bias.defined() ? torch::empty({D}, dy.options()) : torch::Tensor();
+  auto ws = colreduce_workspace(2, D, dy);
   DISPATCH_FLOAT_BF16(dy.scalar_type(), "ls_scatter_bwd", [&] {
     launch_ls_scatter_bwd<scalar_t>(
         (const scalar_t*)dy.data_ptr(), idx.data_ptr<long>(),
@@ -434,12 +449,11 @@ std::vector<torch::Tensor> ls_scatter_bwd(torch::Tensor dy, torch::Tensor idx,
         gamma.defined() ? (const scalar_t*)gamma.data_ptr() : nullptr,
         bias.defined() ? (const scalar_t*)bias.data_ptr() : nullptr,
         scale.defined() && scale.numel() > 0 ? scale.data_ptr<float>() : nullptr,
-        (scalar_t*)dres.data_ptr(),
-        dgamma.defined() ? dgamma.data_ptr<float>() : nullptr,
-        dbias.defined() ? dbias.data_ptr<float>() : nullptr, M, D, current_stream());
+        (scalar_t*)dres.data_ptr(), ws.data_ptr<float>(),
+        dgamma.defined() ? (scalar_t*)dgamma.data_ptr() : nullptr,
+        dbias.defined() ? (scalar_t*)dbias.data_ptr() : nullptr, M, D, current_stream());
   });
-  return {dres, dgamma.defined() ? dgamma.sum(0).to(dy.scalar_type()) : dgamma,
-          dbias.defined() ? dbias.sum(0).to(dy.scalar_type()) : dbias};
+  return {dres, dgamma, dbias};
 }
 
 torch::Tensor swiglu_fwd(torch::Tensor x12) {

@@ -4,163 +4,196 @@
 #include "common.h"
 
 #define EW_BLOCK 256
-// shadow accumulators for the column-reduction backward kernels: per-address
-// atomic RMW chains shrink by this factor (outputs are [EW_SHADOWS, D],
-// summed by the binding)
-#define EW_SHADOWS 32
+// The column-reduction backward kernels (bias_gelu_bwd, ls_*_bwd) run
+// 512-thread blocks on a grid of at most EW_RED_GRID blocks: two blocks per
+// CU, four waves per SIMD, all resident in a single round (their launch bounds
+// hold them to the 128 VGPRs that takes). Each block leaves one row of
+// partial column sums (common.h, two-stage column reduction).
+#define EW_RED_BLOCK 512
+#define EW_RED_GRID 512
+// bias_gelu_fwd: 256-thread blocks, eight per CU (58 VGPRs in bf16: all resident)
+#define EW_FWD_GRID 2048
+static_assert(EW_RED_GRID <= COLRED_MAX_PARTIALS, "workspace holds one row per block");
 
-// fast tanh via the hardware exp pipe: tanh(y) = 1 - 2/(1 + exp(2y)).
-// tanhf() is a slow polyline in libm; __expf is one v_exp_f32 — the GELU
-// kernels were VALU-bound on tanhf in the ViT-L profile.
-DEV_INLINE float fast_tanh(float y) {
-  return 1.0f - 2.0f / (1.0f + __expf(2.0f * y));
+// sigmoid through the hardware exp and reciprocal pipes (v_exp_f32 +
+// v_rcp_f32): no IEEE division sequence. exp overflow gives rcp(inf) = 0.
+DEV_INLINE float fast_sigmoid(float z) {
+  return __builtin_amdgcn_rcpf(1.0f + __expf(-z));
 }
 
+// tanh-approximation GELU (matches torch F.gelu(approximate="tanh")) in its
+// sigmoid form: 0.5*x*(1 + tanh(u)) = x * sigmoid(2u) with
+// 2u = 2*sqrt(2/pi) * (x + 0.044715 x^3). Unlike 1 - 2/(1 + e^2u) this does
+// not cancel for negative x.
 DEV_INLINE float gelu_tanh(float x) {
-  // tanh approximation (matches torch F.gelu(approximate="tanh"))
-  const float k0 = 0.7978845608028654f;  // sqrt(2/pi)
-  const float k1 = 0.044715f;
-  float inner = k0 * (x + k1 * x * x * x);
-  return 0.5f * x * (1.0f + fast_tanh(inner));
+  const float x2 = x * x;
+  return x * fast_sigmoid(x * (1.5957691216f + 0.07135481627f * x2));
 }
 
+// d/dx [x * s(2u)] = s + x * s * (1 - s) * (2u)' = s * (1 + q * (1 - s)),
+// q = x * (2u)' = x * (1.5957691216 + 3 * 0.07135481627 x^2)
 DEV_INLINE float gelu_tanh_grad(float x) {
-  const float k0 = 0.7978845608028654f;
-  const float k1 = 0.044715f;
-  float x2 = x * x;
-  float inner = k0 * (x + k1 * x * x2);
-  float t = fast_tanh(inner);
-  float sech2 = 1.0f - t * t;
-  return 0.5f * (1.0f + t) + 0.5f * x * sech2 * k0 * (1.0f + 3.0f * k1 * x2);
+  const float x2 = x * x;
+  const float s = fast_sigmoid(x * (1.5957691216f + 0.07135481627f * x2));
+  const float q = x * (1.5957691216f + 0.21406444881f * x2);
+  return s * (1.0f + q * (1.0f - s));
+}
+
+// 8 elements of T at p (16-byte aligned) as fp32
+template <typename T>
+DEV_INLINE void load8_f32(const T* p, float* out) {
+  T buf[8];
+  Vec8<T>::load(buf, p);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) out[e] = ScalarOps<T>::load(buf + e);
+}
+
+// Thread layout of the fixed-column kernels: `tpr` threads span a tile of a
+// row, 8 columns each (blockIdx.y tiles wider rows), and the block's other
+// threads take further rows of the same columns ("row lanes"). A thread keeps
+// its columns for the whole walk, so per-column sums stay in registers.
+struct ColLane {
+  int col8;     // first of this thread's 8 columns
+  int c;        // column slot inside the tile
+  int lr;       // this thread's row lane
+  int rl;       // row lanes per block
+  bool active;  // false: past the last row lane or the last column
+};
+
+DEV_INLINE ColLane col_lane(int tpr, int D) {
+  ColLane t;
+  t.rl = blockDim.x / tpr;
+  t.lr = threadIdx.x / tpr;
+  t.c = threadIdx.x - t.lr * tpr;
+  t.col8 = (blockIdx.y * tpr + t.c) * 8;
+  t.active = t.lr < t.rl && t.col8 < D;
+  return t;
+}
+
+// Stage 1 of the column reduction: merge the row lanes' sums of 8 columns
+// through LDS in a fixed order, then store the block's partial as two float4
+// into workspace row blockIdx.x. `red` holds EW_RED_BLOCK * 8 floats. Every
+// thread of the block must call this (it has barriers).
+DEV_INLINE void colred_block_store(float* red, const float* acc, float* __restrict__ ws,
+                                   int D, int tpr, const ColLane& t) {
+  if (t.rl > 1) {
+    __syncthreads();  // a previous accumulator's merge has been read
+    if (t.active && t.lr > 0) {
+      float4_t* r4 = reinterpret_cast<float4_t*>(red + threadIdx.x * 8);
+      r4[0] = float4_t{acc[0], acc[1], acc[2], acc[3]};
+      r4[1] = float4_t{acc[4], acc[5], acc[6], acc[7]};
+    }
+    __syncthreads();
+  }
+  if (t.active && t.lr == 0) {
+    float4_t lo = {acc[0], acc[1], acc[2], acc[3]};
+    float4_t hi = {acc[4], acc[5], acc[6], acc[7]};
+    for (int k = 1; k < t.rl; ++k) {
+      const float4_t* r4 = reinterpret_cast<const float4_t*>(red + (k * tpr + t.c) * 8);
+      lo += r4[0];
+      hi += r4[1];
+    }
+    float4_t* w4 = reinterpret_cast<float4_t*>(ws + (long)blockIdx.x * D + t.col8);
+    w4[0] = lo;
+    w4[1] = hi;
+  }
 }
 
 // ---------------------------- bias + gelu ------------------------------
-// Vectorized 8-wide (H % 8 == 0 — every FFN hidden dim). Backward assigns
-// each thread a FIXED 8-column slice and walks rows, accumulating dbias in
-// registers; one atomicAdd per column per thread at the end (guideline 12).
+// Vectorized 8-wide (H % 8 == 0 — every FFN hidden dim). Forward and backward
+// give each thread a FIXED 8-column slice (no per-element index arithmetic,
+// bias stays in registers) and walk rows, RR rows in flight per iteration:
+// all 16-byte loads of an iteration are issued before the first use. Backward
+// accumulates dbias in registers and leaves it through the two-stage column
+// reduction.
 
-template <typename T>
-__global__ void bias_gelu_fwd_kernel(const T* __restrict__ x, const T* __restrict__ bias,
-                                     T* __restrict__ y, long rows, int H) {
-  const long total8 = rows * (long)(H / 8);
-  for (long idx = blockIdx.x * (long)blockDim.x + threadIdx.x; idx < total8;
-       idx += (long)gridDim.x * blockDim.x) {
-    const int col8 = (int)(idx % (H / 8)) * 8;
-    const T* xp = x + idx * 8;
-    T* yp = y + idx * 8;
-    T xb[8], bb[8], yb[8];
-    Vec8<T>::load(xb, xp);
-    Vec8<T>::load(bb, bias + col8);
+template <typename T, int RR = 4>
+__global__ __launch_bounds__(EW_BLOCK) void bias_gelu_fwd_kernel(
+    const T* __restrict__ x, const T* __restrict__ bias, T* __restrict__ y, long rows, int H,
+    int tpr) {
+  const ColLane t = col_lane(tpr, H);
+  if (!t.active) return;
+  float bb[8];
+  load8_f32(bias + t.col8, bb);
+  long row = ((long)blockIdx.x * t.rl + t.lr) * RR;
+  const long rstep = (long)gridDim.x * t.rl * RR;
+  for (; row + RR - 1 < rows; row += rstep) {
+    T xb[RR][8];
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      float v = ScalarOps<T>::load(xb + e) + ScalarOps<T>::load(bb + e);
-      ScalarOps<T>::store(yb + e, gelu_tanh(v));
-    }
-    Vec8<T>::store(yp, yb);
-  }
-}
-
-template <typename T, int RR_ILP = 4>
-__global__ void bias_gelu_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ x,
-                                     const T* __restrict__ bias, T* __restrict__ dx,
-                                     float* __restrict__ dbias, long rows, int H) {
-  // blockIdx.y tiles columns (256 threads x 8 cols); blockIdx.x strides rows.
-  const int col8 = (blockIdx.y * blockDim.x + threadIdx.x) * 8;
-  if (col8 >= H) return;
-  T bb[8];
-  Vec8<T>::load(bb, bias + col8);
-  float db[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  // RR_ILP rows in flight per iteration: the fixed-column walk is a strided
-  // stream, so batch the loads for ILP/prefetch depth
-  long row = blockIdx.x * (long)RR_ILP;
-  const long rstep = (long)gridDim.x * RR_ILP;
-  for (; row + RR_ILP - 1 < rows; row += rstep) {
-    T xb[RR_ILP][8], gb[RR_ILP][8], ob[RR_ILP][8];
+    for (int rr = 0; rr < RR; ++rr) Vec8<T>::load(xb[rr], x + (row + rr) * (long)H + t.col8);
 #pragma unroll
-    for (int rr = 0; rr < RR_ILP; ++rr) {
-      const long off = (row + rr) * (long)H + col8;
-      Vec8<T>::load(xb[rr], x + off);
-      Vec8<T>::load(gb[rr], dy + off);
-    }
+    for (int rr = 0; rr < RR; ++rr) {
+      float o[8];
 #pragma unroll
-    for (int rr = 0; rr < RR_ILP; ++rr) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        float v = ScalarOps<T>::load(xb[rr] + e) + ScalarOps<T>::load(bb + e);
-        float g = ScalarOps<T>::load(gb[rr] + e) * gelu_tanh_grad(v);
-        ScalarOps<T>::store(ob[rr] + e, g);
-        db[e] += g;
-      }
-      Vec8<T>::store(dx + (row + rr) * (long)H + col8, ob[rr]);
+      for (int e = 0; e < 8; ++e) o[e] = gelu_tanh(ScalarOps<T>::load(xb[rr] + e) + bb[e]);
+      Pack8<T>::store(y + (row + rr) * (long)H + t.col8, o);
     }
   }
   for (; row < rows; ++row) {
-    const long off = row * (long)H + col8;
-    T xb[8], gb[8], ob[8];
-    Vec8<T>::load(xb, x + off);
-    Vec8<T>::load(gb, dy + off);
+    const long off = row * (long)H + t.col8;
+    float v[8], o[8];
+    load8_f32(x + off, v);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      float v = ScalarOps<T>::load(xb + e) + ScalarOps<T>::load(bb + e);
-      float g = ScalarOps<T>::load(gb + e) * gelu_tanh_grad(v);
-      ScalarOps<T>::store(ob + e, g);
-      db[e] += g;
-    }
-    Vec8<T>::store(dx + off, ob);
+    for (int e = 0; e < 8; ++e) o[e] = gelu_tanh(v[e] + bb[e]);
+    Pack8<T>::store(y + off, o);
   }
-  float* dbias_s = dbias + (long)(blockIdx.x & (EW_SHADOWS - 1)) * H;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) atomicAdd(dbias_s + col8 + e, db[e]);
 }
 
-// Contiguous-row bias+GELU backward (A/B variant, DINOV3_BG_ROWS=1): each
-// block walks whole rows (PASSES x 2048-col sweeps, perfectly coalesced
-// 4 KB bursts) instead of a fixed column slice's strided walk; dbias
-// accumulates in registers per (thread, pass) column set and leaves via the
-// shadowed atomics. PASSES = H / (256*8).
-template <typename T, int PASSES>
-__global__ __launch_bounds__(256) void bias_gelu_bwd_rows_kernel(
+template <typename T, int RR = 4>
+__global__ __launch_bounds__(EW_RED_BLOCK, 4) void bias_gelu_bwd_kernel(
     const T* __restrict__ dy, const T* __restrict__ x, const T* __restrict__ bias,
-    T* __restrict__ dx, float* __restrict__ dbias, long rows, int H) {
-  T bb[PASSES][8];
-  float db[PASSES][8];
+    T* __restrict__ dx, float* __restrict__ dbias_ws, long rows, int H, int tpr) {
+  __shared__ float red[EW_RED_BLOCK * 8];
+  const ColLane t = col_lane(tpr, H);
+  float db[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (t.active) {
+    float bb[8];
+    load8_f32(bias + t.col8, bb);
+    long row = ((long)blockIdx.x * t.rl + t.lr) * RR;
+    const long rstep = (long)gridDim.x * t.rl * RR;
+    for (; row + RR - 1 < rows; row += rstep) {
+      T xb[RR][8], gb[RR][8];
 #pragma unroll
-  for (int pss = 0; pss < PASSES; ++pss) {
-    Vec8<T>::load(bb[pss], bias + (pss * 256 + threadIdx.x) * 8);
+      for (int rr = 0; rr < RR; ++rr) {
+        const long off = (row + rr) * (long)H + t.col8;
+        Vec8<T>::load(xb[rr], x + off);
+        Vec8<T>::load(gb[rr], dy + off);
+      }
+      // keep the scheduler from sinking the loads to their uses (it does, to
+      // save registers, and then waits for each in turn)
+      __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) db[pss][e] = 0.f;
-  }
-  for (long row = blockIdx.x; row < rows; row += gridDim.x) {
-    const long base = row * (long)H;
+      for (int rr = 0; rr < RR; ++rr) {
+        float o[8];
 #pragma unroll
-    for (int pss = 0; pss < PASSES; ++pss) {
-      const long off = base + (pss * 256 + threadIdx.x) * 8;
-      T xb[8], gb[8], ob[8];
-      Vec8<T>::load(xb, x + off);
-      Vec8<T>::load(gb, dy + off);
+        for (int e = 0; e < 8; ++e) {
+          const float v = ScalarOps<T>::load(xb[rr] + e) + bb[e];
+          o[e] = ScalarOps<T>::load(gb[rr] + e) * gelu_tanh_grad(v);
+          db[e] += o[e];
+        }
+        Pack8<T>::store(dx + (row + rr) * (long)H + t.col8, o);
+      }
+    }
+    for (; row < rows; ++row) {
+      const long off = row * (long)H + t.col8;
+      float v[8], g[8], o[8];
+      load8_f32(x + off, v);
+      load8_f32(dy + off, g);
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
-        const float v = ScalarOps<T>::load(xb + e) + ScalarOps<T>::load(bb[pss] + e);
-        const float g = ScalarOps<T>::load(gb + e) * gelu_tanh_grad(v);
-        ScalarOps<T>::store(ob + e, g);
-        db[pss][e] += g;
+        o[e] = g[e] * gelu_tanh_grad(v[e] + bb[e]);
+        db[e] += o[e];
       }
-      Vec8<T>::store(dx + off, ob);
+      Pack8<T>::store(dx + off, o);
     }
   }
-  float* dbias_s = dbias + (long)(blockIdx.x & (EW_SHADOWS - 1)) * H;
-#pragma unroll
-  for (int pss = 0; pss < PASSES; ++pss) {
-    const int c8 = (pss * 256 + threadIdx.x) * 8;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) atomicAdd(dbias_s + c8 + e, db[pss][e]);
-  }
+  colred_block_store(red, db, dbias_ws, H, tpr, t);
 }
 
 // -------------------- LayerScale + residual add (K10) -------------------
 // out = x + gamma * res ; bwd: dx = dout (aliased), dres = dout * gamma,
-// dgamma = colsum(dout * res). 8-wide; same fixed-column-slice register
-// accumulation as bias_gelu_bwd.
+// dgamma = colsum(dout * res). 8-wide. The backward is ls_bwd_kernel below,
+// shared with the bias-fused and scatter forms.
 
 template <typename T>
 __global__ void ls_axpy_fwd_kernel(const T* __restrict__ x, const T* __restrict__ res,
@@ -184,57 +217,7 @@ __global__ void ls_axpy_fwd_kernel(const T* __restrict__ x, const T* __restrict_
   }
 }
 
-template <typename T>
-__global__ void ls_axpy_bwd_kernel(const T* __restrict__ dout, const T* __restrict__ res,
-                                   const T* __restrict__ gamma, T* __restrict__ dres,
-                                   float* __restrict__ dgamma, long rows, int D) {
-  const int col8 = (blockIdx.y * blockDim.x + threadIdx.x) * 8;
-  if (col8 >= D) return;
-  T gb[8];
-  Vec8<T>::load(gb, gamma + col8);
-  float dg[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  // 4 rows in flight: with the atomic-chain-capped grid (~384 blocks) a
-  // one-row walk leaves too few loads outstanding to cover HBM latency
-  long row = blockIdx.x * 4L;
-  const long rstep = (long)gridDim.x * 4;
-  for (; row + 3 < rows; row += rstep) {
-    T db[4][8], rb[4][8], ob[4][8];
-#pragma unroll
-    for (int rr = 0; rr < 4; ++rr) {
-      Vec8<T>::load(db[rr], dout + (row + rr) * (long)D + col8);
-      Vec8<T>::load(rb[rr], res + (row + rr) * (long)D + col8);
-    }
-#pragma unroll
-    for (int rr = 0; rr < 4; ++rr) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float g = ScalarOps<T>::load(db[rr] + e);
-        dg[e] += g * ScalarOps<T>::load(rb[rr] + e);
-        ScalarOps<T>::store(ob[rr] + e, g * ScalarOps<T>::load(gb + e));
-      }
-      Vec8<T>::store(dres + (row + rr) * (long)D + col8, ob[rr]);
-    }
-  }
-  for (; row < rows; ++row) {
-    const long off = row * (long)D + col8;
-    T db[8], rb[8], ob[8];
-    Vec8<T>::load(db, dout + off);
-    Vec8<T>::load(rb, res + off);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const float g = ScalarOps<T>::load(db + e);
-      dg[e] += g * ScalarOps<T>::load(rb + e);
-      ScalarOps<T>::store(ob + e, g * ScalarOps<T>::load(gb + e));
-    }
-    Vec8<T>::store(dres + off, ob);
-  }
-  float* dgamma_s = dgamma + (long)(blockIdx.x & (EW_SHADOWS - 1)) * D;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) atomicAdd(dgamma_s + col8 + e, dg[e]);
-}
-
-// ---- bias-fused variants (DINOV3_FUSED_RESIDUAL): out = x + gamma*(res+bias).
-// Separate kernels so the validated ls_axpy binaries above stay untouched.
+// ---- bias-fused variant (DINOV3_FUSED_RESIDUAL): out = x + gamma*(res+bias).
 
 template <typename T>
 __global__ void ls_axpy_bias_fwd_kernel(const T* __restrict__ x, const T* __restrict__ res,
@@ -258,65 +241,6 @@ __global__ void ls_axpy_bias_fwd_kernel(const T* __restrict__ x, const T* __rest
       ScalarOps<T>::store(ob + e, v);
     }
     Vec8<T>::store(out + idx * 8, ob);
-  }
-}
-
-template <typename T>
-__global__ void ls_axpy_bias_bwd_kernel(const T* __restrict__ dout,
-                                        const T* __restrict__ res,
-                                        const T* __restrict__ gamma,
-                                        const T* __restrict__ bias, T* __restrict__ dres,
-                                        float* __restrict__ dgamma,
-                                        float* __restrict__ dbias, long rows, int D) {
-  const int col8 = (blockIdx.y * blockDim.x + threadIdx.x) * 8;
-  if (col8 >= D) return;
-  T gb[8], bb[8];
-  Vec8<T>::load(gb, gamma + col8);
-  Vec8<T>::load(bb, bias + col8);
-  float dg[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  float db_acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  long row = blockIdx.x * 4L;
-  const long rstep = (long)gridDim.x * 4;
-  for (; row + 3 < rows; row += rstep) {
-    T db[4][8], rb[4][8], ob[4][8];
-#pragma unroll
-    for (int rr = 0; rr < 4; ++rr) {
-      Vec8<T>::load(db[rr], dout + (row + rr) * (long)D + col8);
-      Vec8<T>::load(rb[rr], res + (row + rr) * (long)D + col8);
-    }
-#pragma unroll
-    for (int rr = 0; rr < 4; ++rr) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float g = ScalarOps<T>::load(db[rr] + e);
-        const float gm = ScalarOps<T>::load(gb + e);
-        dg[e] += g * (ScalarOps<T>::load(rb[rr] + e) + ScalarOps<T>::load(bb + e));
-        db_acc[e] += g * gm;
-        ScalarOps<T>::store(ob[rr] + e, g * gm);
-      }
-      Vec8<T>::store(dres + (row + rr) * (long)D + col8, ob[rr]);
-    }
-  }
-  for (; row < rows; ++row) {
-    const long off = row * (long)D + col8;
-    T db[8], rb[8], ob[8];
-    Vec8<T>::load(db, dout + off);
-    Vec8<T>::load(rb, res + off);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const float g = ScalarOps<T>::load(db + e);
-      const float gm = ScalarOps<T>::load(gb + e);
-      dg[e] += g * (ScalarOps<T>::load(rb + e) + ScalarOps<T>::load(bb + e));
-      db_acc[e] += g * gm;
-      ScalarOps<T>::store(ob + e, g * gm);
-    }
-    Vec8<T>::store(dres + off, ob);
-  }
-  const long sh = (long)(blockIdx.x & (EW_SHADOWS - 1)) * D;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    atomicAdd(dgamma + sh + col8 + e, dg[e]);
-    atomicAdd(dbias + sh + col8 + e, db_acc[e]);
   }
 }
 
@@ -357,74 +281,85 @@ __global__ void ls_scatter_add_kernel(T* __restrict__ dst, const long* __restric
   }
 }
 
-// backward: dres[r,c] = dy[idx[r],c] * gamma[c] * scale[r];
-//           dgamma[c] += sum_r dy[idx[r],c] * (src[r,c]+bias[c]) * scale[r];
-//           dbias[c]  += sum_r dy[idx[r],c] * gamma[c] * scale[r]
-template <typename T, int RR = 4>
-__global__ void ls_scatter_bwd_kernel(const T* __restrict__ dy, const long* __restrict__ idx,
-                                      const T* __restrict__ src,
-                                      const T* __restrict__ gamma,
-                                      const T* __restrict__ bias,
-                                      const float* __restrict__ scale,
-                                      T* __restrict__ dres, float* __restrict__ dgamma,
-                                      float* __restrict__ dbias, long M, int D) {
-  const int col8 = (blockIdx.y * blockDim.x + threadIdx.x) * 8;
-  if (col8 >= D) return;
-  T gb[8], bb[8];
-  if (gamma != nullptr) Vec8<T>::load(gb, gamma + col8);
-  if (bias != nullptr) Vec8<T>::load(bb, bias + col8);
+// Backward of all three LayerScale residual forms (ls_axpy, ls_axpy_bias,
+// ls_scatter_add), one kernel:
+//   dres[r,c] = dy[row(r),c] * gamma[c] * scale[r]
+//   dgamma[c] = sum_r dy[row(r),c] * (src[r,c] + bias[c]) * scale[r]
+//   dbias[c]  = sum_r dy[row(r),c] * gamma[c] * scale[r]
+// row(r) = idx[r] for the scatter form (INDEXED) and r otherwise. Null gamma /
+// bias / scale read as 1 / 0 / 1; a null workspace skips that sum. Same
+// fixed-column walk and two-stage column reduction as bias_gelu_bwd.
+template <typename T, bool INDEXED, int RR = 4>
+__global__ __launch_bounds__(EW_RED_BLOCK, 4) void ls_bwd_kernel(
+    const T* __restrict__ dy, const long* __restrict__ idx, const T* __restrict__ src,
+    const T* __restrict__ gamma, const T* __restrict__ bias, const float* __restrict__ scale,
+    T* __restrict__ dres, float* __restrict__ dgamma_ws, float* __restrict__ dbias_ws, long M,
+    int D, int tpr) {
+  __shared__ float red[EW_RED_BLOCK * 8];
+  const ColLane t = col_lane(tpr, D);
   float dg[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  float db_acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  long r = blockIdx.x * (long)RR;
-  const long rstep4 = (long)gridDim.x * RR;
-  for (; r + RR - 1 < M; r += rstep4) {
-    long srow[RR];
-    float sc[RR];
-    T dyb[RR][8], rb[RR][8], ob[RR][8];
-#pragma unroll
-    for (int rr = 0; rr < RR; ++rr) {
-      srow[rr] = idx[r + rr];
-      sc[rr] = scale != nullptr ? scale[r + rr] : 1.0f;
-      Vec8<T>::load(dyb[rr], dy + srow[rr] * (long)D + col8);
-      Vec8<T>::load(rb[rr], src + (r + rr) * (long)D + col8);
-    }
-#pragma unroll
-    for (int rr = 0; rr < RR; ++rr) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float gv = ScalarOps<T>::load(dyb[rr] + e) * sc[rr];
-        const float gm = gamma != nullptr ? ScalarOps<T>::load(gb + e) : 1.0f;
-        const float bv = bias != nullptr ? ScalarOps<T>::load(bb + e) : 0.0f;
-        dg[e] += gv * (ScalarOps<T>::load(rb[rr] + e) + bv);
-        db_acc[e] += gv * gm;
-        ScalarOps<T>::store(ob[rr] + e, gv * gm);
-      }
-      Vec8<T>::store(dres + (r + rr) * (long)D + col8, ob[rr]);
-    }
-  }
-  for (; r < M; ++r) {
-    const long srow = idx[r];
-    const float s = scale != nullptr ? scale[r] : 1.0f;
-    T dyb[8], rb[8], ob[8];
-    Vec8<T>::load(dyb, dy + srow * (long)D + col8);
-    Vec8<T>::load(rb, src + r * (long)D + col8);
+  float db[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (t.active) {
+    float gm[8], bv[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      const float gv = ScalarOps<T>::load(dyb + e) * s;
-      const float gm = gamma != nullptr ? ScalarOps<T>::load(gb + e) : 1.0f;
-      const float bv = bias != nullptr ? ScalarOps<T>::load(bb + e) : 0.0f;
-      dg[e] += gv * (ScalarOps<T>::load(rb + e) + bv);
-      db_acc[e] += gv * gm;
-      ScalarOps<T>::store(ob + e, gv * gm);
+      gm[e] = 1.0f;
+      bv[e] = 0.0f;
     }
-    Vec8<T>::store(dres + r * (long)D + col8, ob);
-  }
-  const long sh = (long)(blockIdx.x & (EW_SHADOWS - 1)) * D;
+    if (gamma != nullptr) load8_f32(gamma + t.col8, gm);
+    if (bias != nullptr) load8_f32(bias + t.col8, bv);
+    long r = ((long)blockIdx.x * t.rl + t.lr) * RR;
+    const long rstep = (long)gridDim.x * t.rl * RR;
+    for (; r + RR - 1 < M; r += rstep) {
+      long srow[RR];
+      float sc[RR];
+      T dyb[RR][8], rb[RR][8];
+      // all row indices first: a wait for idx[] between the 16-byte loads
+      // would also wait for every load issued before it
 #pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    if (dgamma != nullptr) atomicAdd(dgamma + sh + col8 + e, dg[e]);
-    if (dbias != nullptr) atomicAdd(dbias + sh + col8 + e, db_acc[e]);
+      for (int rr = 0; rr < RR; ++rr) {
+        srow[rr] = INDEXED ? idx[r + rr] : r + rr;
+        sc[rr] = scale != nullptr ? scale[r + rr] : 1.0f;
+      }
+#pragma unroll
+      for (int rr = 0; rr < RR; ++rr) {
+        Vec8<T>::load(dyb[rr], dy + srow[rr] * (long)D + t.col8);
+        Vec8<T>::load(rb[rr], src + (r + rr) * (long)D + t.col8);
+      }
+      // keep the scheduler from sinking the loads to their uses (it does, to
+      // save registers, and then waits for each in turn)
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int rr = 0; rr < RR; ++rr) {
+        float o[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const float gv = ScalarOps<T>::load(dyb[rr] + e) * sc[rr];
+          dg[e] += gv * (ScalarOps<T>::load(rb[rr] + e) + bv[e]);
+          o[e] = gv * gm[e];
+          db[e] += o[e];
+        }
+        Pack8<T>::store(dres + (r + rr) * (long)D + t.col8, o);
+      }
+    }
+    for (; r < M; ++r) {
+      const long srow = INDEXED ? idx[r] : r;
+      const float s = scale != nullptr ? scale[r] : 1.0f;
+      float g[8], v[8], o[8];
+      load8_f32(dy + srow * (long)D + t.col8, g);
+      load8_f32(src + r * (long)D + t.col8, v);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float gv = g[e] * s;
+        dg[e] += gv * (v[e] + bv[e]);
+        o[e] = gv * gm[e];
+        db[e] += o[e];
+      }
+      Pack8<T>::store(dres + r * (long)D + t.col8, o);
+    }
   }
+  if (dgamma_ws != nullptr) colred_block_store(red, dg, dgamma_ws, D, tpr, t);
+  if (dbias_ws != nullptr) colred_block_store(red, db, dbias_ws, D, tpr, t);
 }
 
 // ------------------------------ swiglu ---------------------------------
@@ -441,7 +376,7 @@ __global__ void swiglu_fwd_kernel(const T* __restrict__ x12, T* __restrict__ y,
     const T* xr = x12 + row * (long)(2 * H);
     float x1 = ScalarOps<T>::load(xr + col);
     float x2 = ScalarOps<T>::load(xr + H + col);
-    float sig = 1.0f / (1.0f + expf(-x1));
+    float sig = __builtin_amdgcn_rcpf(1.0f + expf(-x1));
     ScalarOps<T>::store(y + idx, x1 * sig * x2);
   }
 }
@@ -459,7 +394,7 @@ __global__ void swiglu_bwd_kernel(const T* __restrict__ dy, const T* __restrict_
     float x1 = ScalarOps<T>::load(xr + col);
     float x2 = ScalarOps<T>::load(xr + H + col);
     float g = ScalarOps<T>::load(dy + idx);
-    float sig = 1.0f / (1.0f + expf(-x1));
+    float sig = __builtin_amdgcn_rcpf(1.0f + expf(-x1));
     float silu = x1 * sig;
     float dsilu = sig * (1.0f + x1 * (1.0f - sig));
     ScalarOps<T>::store(dxr + col, g * x2 * dsilu);
@@ -572,42 +507,60 @@ __global__ void rope_fwd_kernel(const T* __restrict__ x, const float* __restrict
 
 // ---------------------------- C wrappers -------------------------------
 
-template <typename T>
-void launch_bias_gelu_fwd(const T* x, const T* bias, T* y, long rows, int H,
-                          hipStream_t stream) {
-  long total8 = rows * (long)(H / 8);
-  int grid = (int)min((total8 + EW_BLOCK - 1) / EW_BLOCK, (long)2048);
-  hipLaunchKernelGGL((bias_gelu_fwd_kernel<T>), dim3(grid), dim3(EW_BLOCK), 0, stream,
-                     x, bias, y, rows, H);
+// Launch geometry of the fixed-column kernels (ColLane): threads per row
+// tile, column tiles (grid.y) and an even row grid (grid.x) of at most
+// max_blocks blocks in all, `rr` rows in flight per row lane.
+struct ColGrid {
+  int tpr, col_tiles, row_grid;
+};
+
+static ColGrid col_grid(long rows, int D, int block, int max_blocks, int rr) {
+  ColGrid g;
+  const int d8 = D / 8;
+  g.tpr = d8 < block ? d8 : block;
+  g.col_tiles = (d8 + g.tpr - 1) / g.tpr;
+  const long rows_per_iter = (long)(block / g.tpr) * rr;
+  const int cap = max_blocks / g.col_tiles > 0 ? max_blocks / g.col_tiles : 1;
+  g.row_grid = even_row_grid((rows + rows_per_iter - 1) / rows_per_iter, cap);
+  return g;
 }
 
 template <typename T>
-void launch_bias_gelu_bwd(const T* dy, const T* x, const T* bias, T* dx, float* dbias,
-                          long rows, int H, hipStream_t stream) {
-  const int col_tiles = (H / 8 + EW_BLOCK - 1) / EW_BLOCK;
-  static const int rowsv = [] {
-    const char* e = getenv("DINOV3_BG_ROWS");
-    return e && e[0] == '1';
-  }();
-  if (rowsv && H == 4096) {
-    int grid = (int)min(rows, (long)2048);
-    hipLaunchKernelGGL((bias_gelu_bwd_rows_kernel<T, 2>), dim3(grid), dim3(256), 0,
-                       stream, dy, x, bias, dx, dbias, rows, H);
-    return;
-  }
-  static const int ilp8 = [] {
-    const char* e = getenv("DINOV3_BG_ILP8");
-    return e && e[0] == '1';
-  }();
-  if (ilp8) {
-    int row_grid = (int)min((rows + 7) / 8, (long)(2048 / col_tiles + 1));
-    hipLaunchKernelGGL((bias_gelu_bwd_kernel<T, 8>), dim3(row_grid, col_tiles),
-                       dim3(EW_BLOCK), 0, stream, dy, x, bias, dx, dbias, rows, H);
-    return;
-  }
-  int row_grid = (int)min((rows + 3) / 4, (long)(2048 / col_tiles + 1));
-  hipLaunchKernelGGL((bias_gelu_bwd_kernel<T, 4>), dim3(row_grid, col_tiles),
-                     dim3(EW_BLOCK), 0, stream, dy, x, bias, dx, dbias, rows, H);
+void launch_bias_gelu_fwd(const T* x, const T* bias, T* y, long rows, int H,
+                          hipStream_t stream) {
+  const ColGrid g = col_grid(rows, H, EW_BLOCK, EW_FWD_GRID, 4);
+  hipLaunchKernelGGL((bias_gelu_fwd_kernel<T, 4>), dim3(g.row_grid, g.col_tiles),
+                     dim3(EW_BLOCK), 0, stream, x, bias, y, rows, H, g.tpr);
+}
+
+// The *_bwd launchers below take `ws`, an fp32 workspace of COLRED_MAX_PARTIALS
+// rows of D per parameter gradient, and write each gradient in T.
+template <typename T>
+void launch_bias_gelu_bwd(const T* dy, const T* x, const T* bias, T* dx, float* ws,
+                          T* dbias, long rows, int H, hipStream_t stream) {
+  const ColGrid g = col_grid(rows, H, EW_RED_BLOCK, EW_RED_GRID, 4);
+  hipLaunchKernelGGL((bias_gelu_bwd_kernel<T, 4>), dim3(g.row_grid, g.col_tiles),
+                     dim3(EW_RED_BLOCK), 0, stream, dy, x, bias, dx, ws, rows, H, g.tpr);
+  launch_colreduce_finalize<T>(ws, dbias, nullptr, nullptr, g.row_grid, H, stream);
+}
+
+// all three LayerScale backward forms; a null dgamma / dbias is not computed
+template <typename T>
+static void launch_ls_bwd(const T* dy, const long* idx, const T* src, const T* gamma,
+                          const T* bias, const float* scale, T* dres, float* ws, T* dgamma,
+                          T* dbias, long M, int D, hipStream_t stream) {
+  const ColGrid g = col_grid(M, D, EW_RED_BLOCK, EW_RED_GRID, 4);
+  float* ws_g = dgamma != nullptr ? ws : nullptr;
+  float* ws_b = dbias != nullptr ? ws + (long)COLRED_MAX_PARTIALS * D : nullptr;
+  if (idx != nullptr)
+    hipLaunchKernelGGL((ls_bwd_kernel<T, true, 4>), dim3(g.row_grid, g.col_tiles),
+                       dim3(EW_RED_BLOCK), 0, stream, dy, idx, src, gamma, bias, scale, dres,
+                       ws_g, ws_b, M, D, g.tpr);
+  else
+    hipLaunchKernelGGL((ls_bwd_kernel<T, false, 4>), dim3(g.row_grid, g.col_tiles),
+                       dim3(EW_RED_BLOCK), 0, stream, dy, idx, src, gamma, bias, scale, dres,
+                       ws_g, ws_b, M, D, g.tpr);
+  launch_colreduce_finalize<T>(ws_g, dgamma, ws_b, dbias, g.row_grid, D, stream);
 }
 
 template <typename T>
@@ -620,15 +573,10 @@ void launch_ls_axpy_fwd(const T* x, const T* res, const T* gamma, T* out, long r
 }
 
 template <typename T>
-void launch_ls_axpy_bwd(const T* dout, const T* res, const T* gamma, T* dres,
-                        float* dgamma, long rows, int D, hipStream_t stream) {
-  // block sized to the row width (no idle half-waves at D=1024) and the
-  // grid bounded: dgamma's per-column atomic chain depth == blocks/shadows
-  const int block = D / 8 < EW_BLOCK ? D / 8 : EW_BLOCK;
-  const int col_tiles = (D / 8 + block - 1) / block;
-  int row_grid = (int)min((rows + 7) / 8, (long)(1024 / col_tiles + 1));
-  hipLaunchKernelGGL((ls_axpy_bwd_kernel<T>), dim3(row_grid, col_tiles), dim3(block),
-                     0, stream, dout, res, gamma, dres, dgamma, rows, D);
+void launch_ls_axpy_bwd(const T* dout, const T* res, const T* gamma, T* dres, float* ws,
+                        T* dgamma, long rows, int D, hipStream_t stream) {
+  launch_ls_bwd<T>(dout, nullptr, res, gamma, nullptr, nullptr, dres, ws, dgamma, nullptr,
+                   rows, D, stream);
 }
 
 template <typename T>
@@ -642,14 +590,10 @@ void launch_ls_axpy_bias_fwd(const T* x, const T* res, const T* gamma, const T* 
 
 template <typename T>
 void launch_ls_axpy_bias_bwd(const T* dout, const T* res, const T* gamma, const T* bias,
-                             T* dres, float* dgamma, float* dbias, long rows, int D,
+                             T* dres, float* ws, T* dgamma, T* dbias, long rows, int D,
                              hipStream_t stream) {
-  const int block = D / 8 < EW_BLOCK ? D / 8 : EW_BLOCK;
-  const int col_tiles = (D / 8 + block - 1) / block;
-  int row_grid = (int)min((rows + 7) / 8, (long)(1024 / col_tiles + 1));
-  hipLaunchKernelGGL((ls_axpy_bias_bwd_kernel<T>), dim3(row_grid, col_tiles),
-                     dim3(block), 0, stream, dout, res, gamma, bias, dres, dgamma,
-                     dbias, rows, D);
+  launch_ls_bwd<T>(dout, nullptr, res, gamma, bias, nullptr, dres, ws, dgamma, dbias, rows,
+                   D, stream);
 }
 
 template <typename T>
@@ -665,16 +609,9 @@ void launch_ls_scatter_add(T* dst, const long* idx, const T* src, const T* gamma
 
 template <typename T>
 void launch_ls_scatter_bwd(const T* dy, const long* idx, const T* src, const T* gamma,
-                           const T* bias, const float* scale, T* dres, float* dgamma,
-                           float* dbias, long M, int D, hipStream_t stream) {
-  const int block = D / 8 < EW_BLOCK ? D / 8 : EW_BLOCK;
-  const int col_tiles = (D / 8 + block - 1) / block;
-  // 4 rows in flight (8 halves occupancy, r2_gpu10) over a 1024-block grid
-  // (2048 measured 34% slower, r2_gpu13); shadows keep atomic chains short
-  int row_grid = (int)min(M > 0 ? (M + 7) / 8 : 1, (long)(1024 / col_tiles + 1));
-  hipLaunchKernelGGL((ls_scatter_bwd_kernel<T, 4>), dim3(row_grid, col_tiles), dim3(block),
-                     0, stream, dy, idx, src, gamma, bias, scale, dres, dgamma, dbias, M,
-                     D);
+                           const T* bias, const float* scale, T* dres, float* ws, T* dgamma,
+                           T* dbias, long M, int D, hipStream_t stream) {
+  launch_ls_bwd<T>(dy, idx, src, gamma, bias, scale, dres, ws, dgamma, dbias, M, D, stream);
 }
 
 template <typename T>
@@ -738,18 +675,18 @@ void launch_rope_fwd(const T* x, const float* sin_t, const float* cos_t, T* y, l
                                         hipStream_t);                                \
   template void launch_ls_axpy_fwd<T>(const T*, const T*, const T*, T*, long, int,   \
                                       hipStream_t);                                  \
-  template void launch_ls_axpy_bwd<T>(const T*, const T*, const T*, T*, float*,      \
+  template void launch_ls_axpy_bwd<T>(const T*, const T*, const T*, T*, float*, T*,  \
                                       long, int, hipStream_t);                       \
   template void launch_ls_axpy_bias_fwd<T>(const T*, const T*, const T*, const T*,   \
                                            T*, long, int, hipStream_t);              \
   template void launch_ls_axpy_bias_bwd<T>(const T*, const T*, const T*, const T*,   \
-                                           T*, float*, float*, long, int,            \
+                                           T*, float*, T*, T*, long, int,            \
                                            hipStream_t);                             \
   template void launch_ls_scatter_add<T>(T*, const long*, const T*, const T*,        \
                                          const T*, const float*, long, int,          \
                                          hipStream_t);                               \
   template void launch_ls_scatter_bwd<T>(const T*, const long*, const T*, const T*,  \
-                                         const T*, const float*, T*, float*, float*, \
+                                         const T*, const float*, T*, float*, T*, T*, \
                                          long, int, hipStream_t);                    \
   template void launch_row_gather<T>(const T*, const long*, T*, long, int,           \
                                      hipStream_t);                                   \
@@ -758,7 +695,7 @@ void launch_rope_fwd(const T* x, const float* sin_t, const float* cos_t, T* y, l
   template void launch_row_gather_scaled<T>(const T*, const long*, const float*, T*, \
                                             long, int, hipStream_t);                 \
   template void launch_bias_gelu_bwd<T>(const T*, const T*, const T*, T*, float*,    \
-                                        long, int, hipStream_t);                     \
+                                        T*, long, int, hipStream_t);                 \
   template void launch_swiglu_fwd<T>(const T*, T*, long, int, hipStream_t);          \
   template void launch_swiglu_bwd<T>(const T*, const T*, T*, long, int, hipStream_t);\
   template void launch_rope_fwd<T>(const T*, const float*, const float*, T*, long,   \

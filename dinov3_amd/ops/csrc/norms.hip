@@ -3,16 +3,16 @@
 //
 // x is [rows, D] contiguous, bf16 or fp32 I/O, fp32 math. One 256-thread
 // block per row (grid-stride over rows). V8=true takes the 8-wide vector
-// path (16 B/lane bf16 loads — guideline 13); weight grads accumulate in
-// registers per fixed column slice in LDS and leave via one atomicAdd per
-// column per block.
+// path (16 B/lane bf16 loads — guideline 13); weight grads accumulate per
+// fixed column slice inside a block and leave through the two-stage column
+// reduction of common.h: one partial row per block, no atomics.
 
 #include "common.h"
 
-// power of two: number of dgamma/dbeta shadow accumulators (see layernorm_bwd)
-#define LN_SHADOWS 32
-
 #define NORM_BLOCK 256
+// row-grid caps of the backward kernels (one workspace row per block)
+#define LN_BWD_GRID 1024
+static_assert(LN_BWD_GRID <= COLRED_MAX_PARTIALS, "workspace holds one row per block");
 
 // block size matched to the row width so no lanes idle in the 8-wide loops
 static inline int norm_block_for(int D) {
@@ -36,10 +36,7 @@ DEV_INLINE void row_load8(const T* p, int i, float* out) {
 template <typename T, bool V8>
 DEV_INLINE void row_store8(T* p, int i, const float* in) {
   if constexpr (V8) {
-    T buf[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) ScalarOps<T>::store(buf + e, in[e]);
-    Vec8<T>::store(p + i, buf);
+    Pack8<T>::store(p + i, in);
   } else {
     ScalarOps<T>::store(p + i, in[0]);
   }
@@ -97,7 +94,7 @@ template <typename T, bool V8>
 __global__ void layernorm_bwd_kernel(
     const T* __restrict__ dy, const T* __restrict__ x, const T* __restrict__ w,
     const float* __restrict__ mean, const float* __restrict__ rstd,
-    T* __restrict__ dx, float* __restrict__ dw, float* __restrict__ db,
+    T* __restrict__ dx, float* __restrict__ dw_ws, float* __restrict__ db_ws,
     long rows, int D) {
   constexpr int EW = V8 ? 8 : 1;
   extern __shared__ float smem[];  // [16 red] + [D dw] + [D db]
@@ -148,60 +145,73 @@ __global__ void layernorm_bwd_kernel(
     }
     __syncthreads();
   }
-  // shadow copies: chain depth of the per-address atomic RMW is
-  // gridDim/shadows instead of gridDim (dw/db are [shadows, D], summed by
-  // the caller)
-  float* dw_s = dw + (long)(blockIdx.x & (LN_SHADOWS - 1)) * D;
-  float* db_s = db + (long)(blockIdx.x & (LN_SHADOWS - 1)) * D;
+  // this block's partial row (the row loop ends on a barrier)
+  float* dw_row = dw_ws + (long)blockIdx.x * D;
+  float* db_row = db_ws + (long)blockIdx.x * D;
   for (int i = threadIdx.x; i < D; i += blockDim.x) {
-    atomicAdd(dw_s + i, dw_acc[i]);
-    atomicAdd(db_s + i, db_acc[i]);
+    dw_row[i] = dw_acc[i];
+    db_row[i] = db_acc[i];
   }
 }
 
 // Wave-per-row LayerNorm backward: each 64-lane wave owns a row, the row's
-// dy/x/w values stay register-cached between the reduction and the dx pass
+// dy/x values stay register-cached between the reduction and the dx pass
 // (ONE read of dy and x instead of two), and the row loop has no block
-// barriers — wave-level __shfl_xor reductions only. Per-wave dgamma/dbeta
-// partials live in LDS and merge once at block end into the shadowed global
-// accumulators. CHUNKS = ceil(D/512) (1: D<=512, 2: 1024, 3: 1536).
+// barriers — wave-level __shfl_xor reductions only. A lane owns the same
+// columns for every row, so w is loaded once and dgamma/dbeta accumulate in
+// registers across the row loop (2 x CHUNKS x 8 floats). LDS serves only the
+// one cross-wave merge at block end, one accumulator at a time, after which
+// the block stores its partial row. CHUNKS = ceil(D/512) (1: D<=512, 2: 1024,
+// 3: 1536).
 template <typename T, int CHUNKS>
 __global__ __launch_bounds__(256) void layernorm_bwd_wave_kernel(
     const T* __restrict__ dy, const T* __restrict__ x, const T* __restrict__ w,
     const float* __restrict__ mean, const float* __restrict__ rstd,
-    T* __restrict__ dx, float* __restrict__ dw, float* __restrict__ db,
+    T* __restrict__ dx, float* __restrict__ dw_ws, float* __restrict__ db_ws,
     long rows, int D) {
   constexpr int NW = 4;  // waves per 256-thread block
   const int wid = threadIdx.x / 64;
   const int lane = threadIdx.x & 63;
-  extern __shared__ float smem[];  // [NW][D] dw partials + [NW][D] db
-  float* dw_acc = smem + (long)wid * D;
-  float* db_acc = smem + (long)(NW + wid) * D;
-  for (int i = lane; i < D; i += 64) {
-    dw_acc[i] = 0.f;
-    db_acc[i] = 0.f;
+  extern __shared__ float smem[];  // [NW][D] merge buffer
+  float wv[CHUNKS][8], dw_acc[CHUNKS][8], db_acc[CHUNKS][8];
+#pragma unroll
+  for (int c = 0; c < CHUNKS; ++c) {
+    const int i = (c * 64 + lane) * 8;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      wv[c][e] = 0.f;
+      dw_acc[c][e] = 0.f;
+      db_acc[c][e] = 0.f;
+    }
+    if (i < D) row_load8<T, true>(w, i, wv[c]);
   }
-  float g[CHUNKS][8], v[CHUNKS][8], wv[CHUNKS][8];
+  const float inv_d = 1.0f / D;
   for (long row = (long)blockIdx.x * NW + wid; row < rows; row += (long)gridDim.x * NW) {
     const T* dyr = dy + row * (long)D;
     const T* xr = x + row * (long)D;
     const float m = mean[row], r = rstd[row];
-    float sum_dyw = 0.f, sum_dyw_xhat = 0.f;
+    float g[CHUNKS][8], xhat[CHUNKS][8];
 #pragma unroll
     for (int c = 0; c < CHUNKS; ++c) {
       const int i = (c * 64 + lane) * 8;
       if (i < D) {
         row_load8<T, true>(dyr, i, g[c]);
-        row_load8<T, true>(xr, i, v[c]);
-        row_load8<T, true>(w, i, wv[c]);
+        row_load8<T, true>(xr, i, xhat[c]);
+      }
+    }
+    float sum_dyw = 0.f, sum_dyw_xhat = 0.f;
+#pragma unroll
+    for (int c = 0; c < CHUNKS; ++c) {
+      const int i = (c * 64 + lane) * 8;
+      if (i < D) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-          const float xhat = (v[c][e] - m) * r;
+          xhat[c][e] = (xhat[c][e] - m) * r;
           const float gw = g[c][e] * wv[c][e];
           sum_dyw += gw;
-          sum_dyw_xhat += gw * xhat;
-          dw_acc[i + e] += g[c][e] * xhat;
-          db_acc[i + e] += g[c][e];
+          sum_dyw_xhat += gw * xhat[c][e];
+          dw_acc[c][e] += g[c][e] * xhat[c][e];
+          db_acc[c][e] += g[c][e];
         }
       }
     }
@@ -210,7 +220,6 @@ __global__ __launch_bounds__(256) void layernorm_bwd_wave_kernel(
       sum_dyw += __shfl_xor(sum_dyw, off, 64);
       sum_dyw_xhat += __shfl_xor(sum_dyw_xhat, off, 64);
     }
-    const float inv_d = 1.0f / D;
     T* dxr = dx + row * (long)D;
 #pragma unroll
     for (int c = 0; c < CHUNKS; ++c) {
@@ -218,25 +227,35 @@ __global__ __launch_bounds__(256) void layernorm_bwd_wave_kernel(
       if (i < D) {
         float o[8];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float xhat = (v[c][e] - m) * r;
-          o[e] = (g[c][e] * wv[c][e] - (sum_dyw + xhat * sum_dyw_xhat) * inv_d) * r;
-        }
+        for (int e = 0; e < 8; ++e)
+          o[e] = (g[c][e] * wv[c][e] - (sum_dyw + xhat[c][e] * sum_dyw_xhat) * inv_d) * r;
         row_store8<T, true>(dxr, i, o);
       }
     }
   }
-  __syncthreads();
-  const long sh = (long)(blockIdx.x & (LN_SHADOWS - 1)) * D;
-  for (int i = threadIdx.x; i < D; i += 256) {
-    float a = 0.f, bsum = 0.f;
+  // cross-wave merge in a fixed order, dgamma then dbeta through one buffer
 #pragma unroll
-    for (int w2 = 0; w2 < NW; ++w2) {
-      a += smem[(long)w2 * D + i];
-      bsum += smem[(long)(NW + w2) * D + i];
+  for (int pass = 0; pass < 2; ++pass) {
+    if (pass == 1) __syncthreads();  // dgamma's merge has been read
+#pragma unroll
+    for (int c = 0; c < CHUNKS; ++c) {
+      const int i = (c * 64 + lane) * 8;
+      if (i < D) {
+        const float* a = pass == 0 ? dw_acc[c] : db_acc[c];
+        float4_t* s4 = reinterpret_cast<float4_t*>(smem + (long)wid * D + i);
+        s4[0] = float4_t{a[0], a[1], a[2], a[3]};
+        s4[1] = float4_t{a[4], a[5], a[6], a[7]};
+      }
     }
-    atomicAdd(dw + sh + i, a);
-    atomicAdd(db + sh + i, bsum);
+    __syncthreads();
+    float* out_row = (pass == 0 ? dw_ws : db_ws) + (long)blockIdx.x * D;
+    for (int i = threadIdx.x * 4; i < D; i += 256 * 4) {
+      float4_t a = *reinterpret_cast<const float4_t*>(smem + i);
+#pragma unroll
+      for (int w2 = 1; w2 < NW; ++w2)
+        a += *reinterpret_cast<const float4_t*>(smem + (long)w2 * D + i);
+      *reinterpret_cast<float4_t*>(out_row + i) = a;
+    }
   }
 }
 
@@ -276,7 +295,7 @@ __global__ void rmsnorm_fwd_kernel(
 template <typename T, bool V8>
 __global__ void rmsnorm_bwd_kernel(
     const T* __restrict__ dy, const T* __restrict__ x, const T* __restrict__ w,
-    const float* __restrict__ rstd, T* __restrict__ dx, float* __restrict__ dw,
+    const float* __restrict__ rstd, T* __restrict__ dx, float* __restrict__ dw_ws,
     long rows, int D) {
   constexpr int EW = V8 ? 8 : 1;
   extern __shared__ float smem[];
@@ -314,7 +333,8 @@ __global__ void rmsnorm_bwd_kernel(
     }
     __syncthreads();
   }
-  for (int i = threadIdx.x; i < D; i += blockDim.x) atomicAdd(dw + i, dw_acc[i]);
+  float* dw_row = dw_ws + (long)blockIdx.x * D;
+  for (int i = threadIdx.x; i < D; i += blockDim.x) dw_row[i] = dw_acc[i];
 }
 
 // ------------------------------ L2 norm --------------------------------
@@ -405,33 +425,42 @@ void launch_layernorm_fwd(const T* x, const T* w, const T* b, T* y, float* mean,
                                      rows, D, eps));
 }
 
+// dw / db come out in T; `ws` is an fp32 workspace of 2 * COLRED_MAX_PARTIALS
+// rows of D (dgamma partials, then dbeta partials).
 template <typename T>
 void launch_layernorm_bwd(const T* dy, const T* x, const T* w, const float* mean,
-                          const float* rstd, T* dx, float* dw, float* db, long rows,
+                          const float* rstd, T* dx, float* ws, T* dw, T* db, long rows,
                           int D, hipStream_t stream) {
+  float* dw_ws = ws;
+  float* db_ws = ws + (long)COLRED_MAX_PARTIALS * D;
+  int grid;
   if (D % 8 == 0 && D <= 1536) {
-    // wave-per-row: one read of dy/x, no block barriers in the row loop
-    int grid = (int)min((rows + 3) / 4, (long)2048);
-    size_t shmem = 2 * 4 * (size_t)D * sizeof(float);
+    // wave-per-row: one read of dy/x, no block barriers in the row loop.
+    // Four blocks per CU (four waves per SIMD at the 120 VGPRs of D = 1024;
+    // three at the 166 VGPRs of D = 1536), every block the same number of
+    // row rounds.
+    grid = even_row_grid((rows + 3) / 4, D <= 1024 ? LN_BWD_GRID : LN_BWD_GRID * 3 / 4);
+    size_t shmem = 4 * (size_t)D * sizeof(float);
     if (D <= 512)
       hipLaunchKernelGGL(HIP_KERNEL_NAME(layernorm_bwd_wave_kernel<T, 1>), dim3(grid),
-                         dim3(256), shmem, stream, dy, x, w, mean, rstd, dx, dw, db,
+                         dim3(256), shmem, stream, dy, x, w, mean, rstd, dx, dw_ws, db_ws,
                          rows, D);
     else if (D <= 1024)
       hipLaunchKernelGGL(HIP_KERNEL_NAME(layernorm_bwd_wave_kernel<T, 2>), dim3(grid),
-                         dim3(256), shmem, stream, dy, x, w, mean, rstd, dx, dw, db,
+                         dim3(256), shmem, stream, dy, x, w, mean, rstd, dx, dw_ws, db_ws,
                          rows, D);
     else
       hipLaunchKernelGGL(HIP_KERNEL_NAME(layernorm_bwd_wave_kernel<T, 3>), dim3(grid),
-                         dim3(256), shmem, stream, dy, x, w, mean, rstd, dx, dw, db,
+                         dim3(256), shmem, stream, dy, x, w, mean, rstd, dx, dw_ws, db_ws,
                          rows, D);
-    return;
+  } else {
+    grid = even_row_grid(rows, LN_BWD_GRID);
+    size_t shmem = (16 + 2 * (size_t)D) * sizeof(float);
+    DISPATCH_V8(D, hipLaunchKernelGGL(HIP_KERNEL_NAME(layernorm_bwd_kernel<T, V8>), dim3(grid),
+                                       dim3(norm_block_for(D)), shmem, stream, dy, x, w, mean,
+                                       rstd, dx, dw_ws, db_ws, rows, D));
   }
-  int grid = (int)min(rows, (long)2048);
-  size_t shmem = (16 + 2 * (size_t)D) * sizeof(float);
-  DISPATCH_V8(D, hipLaunchKernelGGL(HIP_KERNEL_NAME(layernorm_bwd_kernel<T, V8>), dim3(grid),
-                                     dim3(norm_block_for(D)), shmem, stream, dy, x, w, mean,
-                                     rstd, dx, dw, db, rows, D));
+  launch_colreduce_finalize<T>(dw_ws, dw, db_ws, db, grid, D, stream);
 }
 
 template <typename T>
@@ -445,12 +474,13 @@ void launch_rmsnorm_fwd(const T* x, const T* w, T* y, float* rstd, long rows, in
 
 template <typename T>
 void launch_rmsnorm_bwd(const T* dy, const T* x, const T* w, const float* rstd, T* dx,
-                        float* dw, long rows, int D, hipStream_t stream) {
-  int grid = (int)min(rows, (long)2048);
+                        float* ws, T* dw, long rows, int D, hipStream_t stream) {
+  int grid = even_row_grid(rows, LN_BWD_GRID);
   size_t shmem = (16 + (size_t)D) * sizeof(float);
   DISPATCH_V8(D, hipLaunchKernelGGL(HIP_KERNEL_NAME(rmsnorm_bwd_kernel<T, V8>), dim3(grid),
                                      dim3(norm_block_for(D)), shmem, stream, dy, x, w, rstd, dx,
-                                     dw, rows, D));
+                                     ws, rows, D));
+  launch_colreduce_finalize<T>(ws, dw, nullptr, nullptr, grid, D, stream);
 }
 
 template <typename T>
@@ -475,12 +505,12 @@ void launch_l2norm_bwd(const T* dy, const T* y, const float* s, T* dx, long rows
   template void launch_layernorm_fwd<T>(const T*, const T*, const T*, T*, float*, float*, \
                                         long, int, float, hipStream_t);                   \
   template void launch_layernorm_bwd<T>(const T*, const T*, const T*, const float*,       \
-                                        const float*, T*, float*, float*, long, int,      \
+                                        const float*, T*, float*, T*, T*, long, int,      \
                                         hipStream_t);                                     \
   template void launch_rmsnorm_fwd<T>(const T*, const T*, T*, float*, long, int, float,   \
                                       hipStream_t);                                       \
   template void launch_rmsnorm_bwd<T>(const T*, const T*, const T*, const float*, T*,     \
-                                      float*, long, int, hipStream_t);                    \
+                                      float*, T*, long, int, hipStream_t);                \
   template void launch_l2norm_fwd<T>(const T*, T*, float*, long, int, float, hipStream_t);\
   template void launch_l2norm_bwd<T>(const T*, const T*, const float*, T*, long, int,     \
                                      float, hipStream_t);

@@ -1,7 +1,7 @@
 """Per-kernel micro-benchmarks: each HIP op vs its plain-torch counterpart.
 
 GPU-only. Usage (on a GPU box):
-    python tools/bench_kernels.py [--iters 50] [--shape-set vitl]
+    python tools/bench_kernels.py [--iters 50] [--streaming-only]
 
 Prints one line per op: name, HIP us, torch us, speedup, effective GB/s of
 the HIP path (bytes moved at the op's minimum traffic).
@@ -39,6 +39,8 @@ def row(name, hip_us, ref_us, bytes_moved):
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--iters", type=int, default=50)
+    p.add_argument("--streaming-only", action="store_true",
+                   help="stop after the memory-streaming kernels (norms, bias+GELU, LayerScale)")
     args = p.parse_args()
     assert torch.cuda.is_available(), "GPU required"
     dev = "cuda"
@@ -79,6 +81,69 @@ def main():
         timeit(lambda: l2_normalize(x[:8192, :256]), it),
         timeit(lambda: torch.nn.functional.normalize(x[:8192, :256].float(), dim=-1), it),
         8192 * 256 * 2 * 2)
+
+    # The streaming kernels at the flagship's real row counts: drop_path 0.3
+    # keeps 89 of 128 global and 358 of 512 local crops, so the student MLP /
+    # residual / norm kernels see RS rows and the teacher's RT. Bytes are the
+    # minimum traffic: each [rows, width] bf16 operand read or written once.
+    RS, RT = 89 * 197 + 358 * 37, 64 * (197 * 2)
+    for tag, rows in (("student", RS), ("teacher", RT)):
+        hs = torch.randn(rows, H4, device=dev).bfloat16()
+        row(f"bias_gelu_fwd [{rows},4096] {tag}",
+            timeit(lambda: ops.bias_gelu_fwd(hs, hb), it),
+            timeit(lambda: torch.nn.functional.gelu(hs + hb, approximate="tanh"), it),
+            2 * rows * H4 * 2)
+    hs = torch.randn(RS, H4, device=dev).bfloat16()
+    dhs = torch.randn_like(hs)
+
+    def gelu_bwd_ref():
+        v = (hs + hb).float()
+        t = torch.tanh(0.7978845608 * (v + 0.044715 * v ** 3))
+        d = 0.5 * (1 + t) + 0.5 * v * (1 - t * t) * 0.7978845608 * (1 + 0.134145 * v * v)
+        g = dhs.float() * d
+        return g.bfloat16(), g.sum(0).bfloat16()
+
+    row(f"bias_gelu_bwd [{RS},4096]",
+        timeit(lambda: ops.bias_gelu_bwd(dhs, hs, hb), it),
+        timeit(gelu_bwd_ref, max(it // 4, 3)),
+        3 * RS * H4 * 2)
+
+    xs = torch.randn(RS, D, device=dev).bfloat16()
+    dflat = torch.randn(R, D, device=dev).bfloat16()
+    keep = torch.randperm(R, device=dev)[:RS]
+    sc = torch.full((RS,), 1.0 / 0.7, device=dev)
+    lb = torch.randn(D, device=dev).bfloat16()
+
+    def ls_scatter_bwd_ref():
+        gv = dflat[keep].float() * sc[:, None]
+        return ((gv * gamma.float()).bfloat16(), (gv * (xs.float() + lb.float())).sum(0),
+                (gv * gamma.float()).sum(0))
+
+    row(f"ls_scatter_bwd [{RS},1024]",
+        timeit(lambda: ops.ls_scatter_bwd(dflat, keep, xs, gamma, lb, sc), it),
+        timeit(ls_scatter_bwd_ref, it),
+        3 * RS * D * 2)
+
+    wl = torch.randn(D, device=dev).bfloat16()
+    row(f"layernorm_fwd [{RS},1024]",
+        timeit(lambda: ops.layernorm_fwd(xs, wl, b, 1e-6), it),
+        timeit(lambda: torch.nn.functional.layer_norm(xs, (D,), wl, b, 1e-6), it),
+        2 * RS * D * 2)
+    _, ln_mean, ln_rstd = ops.layernorm_fwd(xs, wl, b, 1e-6)
+    dys = torch.randn_like(xs)
+    xg = xs.detach().requires_grad_(True)
+    wg, bg = wl.detach().requires_grad_(True), b.detach().requires_grad_(True)
+
+    def ln_bwd_ref():
+        y = torch.nn.functional.layer_norm(xg, (D,), wg, bg, 1e-6)
+        return torch.autograd.grad(y, (xg, wg, bg), dys)
+
+    row(f"layernorm_bwd [{RS},1024] (torch: f+b)",
+        timeit(lambda: ops.layernorm_bwd(dys, xs, wl, ln_mean, ln_rstd), it),
+        timeit(ln_bwd_ref, it),
+        3 * RS * D * 2)
+    if args.streaming_only:
+        return
 
     # FMHA fwd: global-crop group
     from dinov3_amd.ops.flat_attention import flat_multi_fmha
