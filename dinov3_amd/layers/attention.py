@@ -15,10 +15,10 @@ from typing import List, Optional, Tuple
 
 import torch
 import torch.nn as nn
-import torch.nn.functional as F
 
 from ..ops.flat_attention import GroupMeta, flat_multi_fmha
 from ..utils.utils import cat_keep_shapes, uncat_with_shapes
+from .fp8_linear import linear_call, linear_op
 
 RopeSinCos = Tuple[torch.Tensor, torch.Tensor]
 
@@ -36,7 +36,7 @@ class LinearKMaskedBias(nn.Linear):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         b = self.bias * self.bias_mask.to(self.bias.dtype) if self.bias is not None else None
-        return F.linear(x, self.weight, b)
+        return linear_op(self, x, self.weight, b)
 
 
 class SelfAttention(nn.Module):
@@ -66,13 +66,11 @@ class SelfAttention(nn.Module):
 
         skip_proj_bias: leave the out-projection bias off the GEMM — the
         caller folds it into the residual kernel (ops/fused_residual.py)."""
-        qkv_flat = self.qkv(flat)
+        qkv_flat = linear_call(self.qkv, flat)
         ctx_flat = flat_multi_fmha(qkv_flat, self.num_heads, metas)
         if skip_proj_bias:
-            import torch.nn.functional as F
-
-            return self.proj_drop(F.linear(ctx_flat, self.proj.weight))
-        return self.proj_drop(self.proj(ctx_flat))
+            return self.proj_drop(linear_op(self.proj, ctx_flat, self.proj.weight))
+        return self.proj_drop(linear_call(self.proj, ctx_flat))
 
     @staticmethod
     def _meta_for(x: torch.Tensor, rope: Optional[RopeSinCos], offset: int) -> GroupMeta:

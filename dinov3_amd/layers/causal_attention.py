@@ -11,6 +11,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .ffn_layers import Mlp
+from .fp8_linear import linear_call
 from .norms import LayerNorm, LayerScale
 
 
@@ -27,7 +28,7 @@ class CausalSelfAttention(nn.Module):
 
     def forward(self, x: torch.Tensor, is_causal: bool = True) -> torch.Tensor:
         B, N, D = x.shape
-        qkv = self.qkv(x).reshape(B, N, 3, self.num_heads, self.head_dim)
+        qkv = linear_call(self.qkv, x).reshape(B, N, 3, self.num_heads, self.head_dim)
         q, k, v = qkv.permute(2, 0, 3, 1, 4).unbind(0)
         s = torch.einsum("bhqd,bhkd->bhqk", q.float(), k.float()) / math.sqrt(self.head_dim)
         if is_causal:
@@ -38,7 +39,7 @@ class CausalSelfAttention(nn.Module):
             p = F.dropout(p, p=self.attn_drop)
         o = torch.einsum("bhqk,bhkd->bhqd", p, v.float()).to(x.dtype)
         o = o.permute(0, 2, 1, 3).reshape(B, N, D)
-        return self.proj(o)
+        return linear_call(self.proj, o)
 
 
 class CausalSelfAttentionBlock(nn.Module):

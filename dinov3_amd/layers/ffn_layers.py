@@ -9,10 +9,10 @@ from __future__ import annotations
 
 import torch
 import torch.nn as nn
-import torch.nn.functional as F
 
 from ..ops import bias_gelu
 from ..ops.bias_act import swiglu_gate
+from .fp8_linear import linear_call, linear_op
 
 
 class Mlp(nn.Module):
@@ -31,12 +31,12 @@ class Mlp(nn.Module):
         # forward would leave backward without the pre-activation. See
         # ops/csrc/blaslt_ext.hip and docs/KERNELS.md.)
         # skip_out_bias: caller folds fc2's bias into the residual kernel.
-        h = F.linear(x, self.fc1.weight)
+        h = linear_op(self.fc1, x, self.fc1.weight)
         h = bias_gelu(h, self.fc1.bias)
         h = self.drop(h)
         if skip_out_bias:
-            return self.drop(F.linear(h, self.fc2.weight))
-        return self.drop(self.fc2(h))
+            return self.drop(linear_op(self.fc2, h, self.fc2.weight))
+        return self.drop(linear_call(self.fc2, h))
 
 
 class SwiGLUFFN(nn.Module):
@@ -54,9 +54,9 @@ class SwiGLUFFN(nn.Module):
         self.drop = nn.Dropout(drop) if drop > 0 else nn.Identity()
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        x12 = self.w12(x)
+        x12 = linear_call(self.w12, x)
         h = swiglu_gate(x12)
-        return self.drop(self.w3(h))
+        return self.drop(linear_call(self.w3, h))
 
 
 FFN_LAYERS = {

@@ -113,6 +113,11 @@ void launch_patch_embed_fwd(const __hip_bfloat16*, const __hip_bfloat16*,
                             const __hip_bfloat16*, __hip_bfloat16*, int, int, int, int,
                             int, int, hipStream_t);
 void launch_probe_mfma(const __hip_bfloat16*, const __hip_bfloat16*, float*, hipStream_t);
+void launch_fp8_quant_rows(const __hip_bfloat16*, unsigned char*, float*, long, int,
+                           hipStream_t);
+void launch_fp8_gemm_nt(const unsigned char*, const float*, const unsigned char*, const float*,
+                        const __hip_bfloat16*, __hip_bfloat16*, long, int, int, hipStream_t);
+void launch_probe_mfma_fp8(const unsigned char*, const unsigned char*, float*, hipStream_t);
 void launch_fmha_fwd(const __hip_bfloat16*, const __hip_bfloat16*, const __hip_bfloat16*,
                      __hip_bfloat16*, float*, int, int, int, float, hipStream_t);
 void launch_fmha_bwd_pre(const __hip_bfloat16*, const __hip_bfloat16*, float*, long, int,
@@ -1041,6 +1046,80 @@ torch::Tensor multi_tensor_l2norm_sq(std::vector<torch::Tensor> g) {
   return out;
 }
 
+// ------------------------------ fp8 forward -----------------------------
+
+// bf16 [M,K] -> (e4m3fn bytes [M,K] as uint8, fp32 power-of-two scales [M]).
+std::vector<torch::Tensor> fp8_quant_rows(torch::Tensor x) {
+  CHECK_INPUT(x);
+  TORCH_CHECK(x.scalar_type() == at::ScalarType::BFloat16, "fp8_quant_rows: x must be bf16");
+  TORCH_CHECK(x.dim() == 2, "fp8_quant_rows: x must be [M, K]");
+  const long M = x.size(0);
+  const long K = x.size(1);
+  TORCH_CHECK(K > 0 && K % FP8_QUANT_VEC == 0 && K <= INT_MAX,
+              "fp8_quant_rows: K must be a positive multiple of ", FP8_QUANT_VEC);
+  TORCH_CHECK((uintptr_t)x.data_ptr() % 16 == 0, "fp8_quant_rows: x must be 16-byte aligned");
+  auto q = torch::empty({M, K}, x.options().dtype(torch::kUInt8));
+  auto scale = torch::empty({M}, x.options().dtype(torch::kFloat));
+  launch_fp8_quant_rows((const __hip_bfloat16*)x.data_ptr(), q.data_ptr<uint8_t>(),
+                        scale.data_ptr<float>(), M, (int)K, current_stream());
+  return {q, scale};
+}
+
+// y[M,N] = bf16((xq . wq^T) * sx[m] * sw[n] + bias[n]); xq [M,K], wq [N,K] e4m3fn bytes.
+torch::Tensor fp8_gemm_nt(torch::Tensor xq, torch::Tensor sx, torch::Tensor wq,
+                          torch::Tensor sw, c10::optional<torch::Tensor> bias) {
+  CHECK_INPUT(xq);
+  CHECK_INPUT(sx);
+  CHECK_INPUT(wq);
+  CHECK_INPUT(sw);
+  TORCH_CHECK(xq.scalar_type() == at::ScalarType::Byte && wq.scalar_type() == at::ScalarType::Byte,
+              "fp8_gemm_nt: operands are e4m3fn bytes viewed as uint8");
+  TORCH_CHECK(sx.scalar_type() == at::ScalarType::Float && sw.scalar_type() == at::ScalarType::Float,
+              "fp8_gemm_nt: scales must be fp32");
+  TORCH_CHECK(xq.dim() == 2 && wq.dim() == 2 && xq.size(1) == wq.size(1),
+              "fp8_gemm_nt: xq [M,K] and wq [N,K] must share K");
+  const long M = xq.size(0);
+  const long N = wq.size(0);
+  const long K = xq.size(1);
+  TORCH_CHECK(K > 0 && K % FP8_GEMM_BK == 0 && K <= INT_MAX,
+              "fp8_gemm_nt: K must be a positive multiple of ", FP8_GEMM_BK);
+  TORCH_CHECK(N > 0 && N % FP8_GEMM_N_ALIGN == 0 && N <= INT_MAX,
+              "fp8_gemm_nt: N must be a positive multiple of ", FP8_GEMM_N_ALIGN);
+  TORCH_CHECK(sx.numel() == M && sw.numel() == N, "fp8_gemm_nt: one scale per row");
+  TORCH_CHECK((uintptr_t)xq.data_ptr() % 16 == 0 && (uintptr_t)wq.data_ptr() % 16 == 0 &&
+                  (uintptr_t)sw.data_ptr() % 16 == 0,
+              "fp8_gemm_nt: operands must be 16-byte aligned");
+  const __hip_bfloat16* bias_ptr = nullptr;
+  torch::Tensor b;
+  if (bias.has_value() && bias->defined()) {
+    b = *bias;
+    CHECK_INPUT(b);
+    TORCH_CHECK(b.scalar_type() == at::ScalarType::BFloat16 && b.numel() == N,
+                "fp8_gemm_nt: bias must be bf16 [N]");
+    if ((uintptr_t)b.data_ptr() % 8 != 0) b = b.clone();
+    bias_ptr = (const __hip_bfloat16*)b.data_ptr();
+  }
+  auto y = torch::empty({M, N}, xq.options().dtype(torch::kBFloat16));
+  launch_fp8_gemm_nt(xq.data_ptr<uint8_t>(), sx.data_ptr<float>(), wq.data_ptr<uint8_t>(),
+                     sw.data_ptr<float>(), bias_ptr, (__hip_bfloat16*)y.data_ptr(), M, (int)N,
+                     (int)K, current_stream());
+  return y;
+}
+
+// One-wave lane-map probe: c[16,16] = a[16,128] . bt[16,128]^T on e4m3fn bytes.
+torch::Tensor probe_mfma_fp8(torch::Tensor a, torch::Tensor bt) {
+  CHECK_INPUT(a);
+  CHECK_INPUT(bt);
+  TORCH_CHECK(a.scalar_type() == at::ScalarType::Byte && bt.scalar_type() == at::ScalarType::Byte);
+  TORCH_CHECK(a.dim() == 2 && a.size(0) == 16 && a.size(1) == FP8_GEMM_BK &&
+                  bt.dim() == 2 && bt.size(0) == 16 && bt.size(1) == FP8_GEMM_BK,
+              "probe_mfma_fp8: a and bt must be [16, ", FP8_GEMM_BK, "]");
+  auto c = torch::empty({16, 16}, a.options().dtype(torch::kFloat));
+  launch_probe_mfma_fp8(a.data_ptr<uint8_t>(), bt.data_ptr<uint8_t>(), c.data_ptr<float>(),
+                        current_stream());
+  return c;
+}
+
 }  // namespace
 
 // hipBLASLt fused-epilogue entry points (blaslt_ext.hip)
@@ -1078,6 +1157,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("swiglu_bwd", &swiglu_bwd);
   mod.def("rope_fwd", &rope_fwd);
   mod.def("probe_mfma", &probe_mfma);
+  mod.def("fp8_quant_rows", &fp8_quant_rows);
+  mod.def("fp8_gemm_nt", &fp8_gemm_nt);
+  mod.def("probe_mfma_fp8", &probe_mfma_fp8);
   mod.def("patch_embed_fwd", &patch_embed_fwd);
   mod.def("dino_ce_fwd", &dino_ce_fwd);
   mod.def("dino_ce_bwd", &dino_ce_bwd);

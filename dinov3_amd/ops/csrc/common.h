@@ -202,6 +202,16 @@ static inline void launch_colreduce_finalize(const float* part0, T* out0, const 
                      n_partials, D);
 }
 
+// ---- FP8 forward GEMM (fp8_gemm.hip) ----
+// Tile geometry and shape preconditions, shared by the kernels, their
+// launchers and the bindings' TORCH_CHECKs.
+#define FP8_GEMM_BM 128       // output rows per block
+#define FP8_GEMM_BN 128       // output columns per block
+#define FP8_GEMM_BK 128       // e4m3 bytes of K per stage (one scaled MFMA deep)
+#define FP8_GEMM_THREADS 256  // 4 waves, 2 (M) x 2 (N), 64x64 outputs each
+#define FP8_GEMM_N_ALIGN 16   // N must be a multiple of one MFMA tile
+#define FP8_QUANT_VEC 8       // bf16 elements per 16-byte quantiser load
+
 #define HIP_CHECK_LAUNCH()                                                    \
   do {                                                                        \
     hipError_t e = hipGetLastError();                                         \

@@ -16,6 +16,7 @@ import torch
 import torch.nn as nn
 
 from ..layers.dino_head import DINOHead
+from ..layers.fp8_linear import convert_linears_to_fp8, fp8_env_enabled
 from ..loss import DINOLoss, GramLoss, KoLeoLoss, KoLeoLossDistributed, iBOTPatchLoss
 from ..models import build_model_from_cfg
 from ..ops import ema_update_
@@ -33,13 +34,6 @@ class SSLMetaArch(nn.Module):
         assert config.ibot.separate_head is True
         assert config.train.centering == "sinkhorn_knopp"
 
-        if config.student.fp8_enabled:
-            # Parity with the reference, whose fp8 path is commented out and
-            # silently ignored (dinov3_jax/models/__init__.py:42,53) — warn
-            # instead of failing so its vit7b recipes run as they do there.
-            logger.warning("student.fp8_enabled=True requested, but the fp8 "
-                           "linear path is not implemented (the reference "
-                           "ignores this flag too); training continues in bf16")
         student_backbone, teacher_backbone, embed_dim = build_model_from_cfg(config)
         self.student_backbone = student_backbone
         self.teacher_backbone = teacher_backbone
@@ -160,6 +154,17 @@ class SSLMetaArch(nn.Module):
             module.requires_grad_(False)
         if self.gram_backbone is not None:
             self.gram_backbone.requires_grad_(False)
+
+        # FP8 forward for the block linears of both towers (what the reference
+        # intended: init_fp8 on teacher and student, commented out in
+        # dinov3_jax/models/__init__.py:42,53). Heads, patch embed and the gram
+        # teacher stay bf16; backward stays bf16. DINOV3_FP8=1 switches it on
+        # without a config change (for timing the stock benchmark).
+        self.fp8_enabled = bool(config.student.fp8_enabled) or fp8_env_enabled()
+        if self.fp8_enabled:
+            fp8_filter = config.student.get("fp8_filter", "blocks") or "blocks"
+            for backbone in (self.student_backbone, self.teacher_backbone):
+                convert_linears_to_fp8(backbone, fp8_filter)
 
     # ------------------------------------------------------------------
     def _weight_schedule(self, sched_cfg):
