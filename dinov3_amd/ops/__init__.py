@@ -29,10 +29,13 @@ from .proto_scores import dino_softmax_ce, ibot_softmax_ce, sinkhorn_knopp
 from .ls_axpy import ls_axpy
 from .row_ops import gather_rows, scatter_add_rows
 from .flat_attention import flat_multi_fmha
-from .fp8_linear import fp8_eligible, fp8_linear, fp8_quantize_rows
+from .fp8_linear import (fp8_bwd_eligible, fp8_eligible, fp8_linear, fp8_quantize_cols_t,
+                         fp8_quantize_rows)
 
 __all__ = [
     "fp8_quantize_rows",
+    "fp8_quantize_cols_t",
+    "fp8_bwd_eligible",
     "fp8_linear",
     "fp8_eligible",
     "layer_norm",

@@ -113,11 +113,16 @@ void launch_patch_embed_fwd(const __hip_bfloat16*, const __hip_bfloat16*,
                             const __hip_bfloat16*, __hip_bfloat16*, int, int, int, int,
                             int, int, hipStream_t);
 void launch_probe_mfma(const __hip_bfloat16*, const __hip_bfloat16*, float*, hipStream_t);
-void launch_fp8_quant_rows(const __hip_bfloat16*, unsigned char*, float*, long, int,
+void launch_fp8_quant_rows(const __hip_bfloat16*, unsigned char*, float*, long, int, int,
                            hipStream_t);
+int fp8_cols_partials(long, int);
+void launch_fp8_quant_cols_t(const __hip_bfloat16*, unsigned char*, float*, float*, float*,
+                             float*, long, int, int, hipStream_t);
 void launch_fp8_gemm_nt(const unsigned char*, const float*, const unsigned char*, const float*,
-                        const __hip_bfloat16*, __hip_bfloat16*, long, int, int, hipStream_t);
-void launch_probe_mfma_fp8(const unsigned char*, const unsigned char*, float*, hipStream_t);
+                        const __hip_bfloat16*, __hip_bfloat16*, long, int, int, int,
+                        hipStream_t);
+void launch_probe_mfma_fp8(const unsigned char*, const unsigned char*, float*, int, int,
+                           hipStream_t);
 void launch_fmha_fwd(const __hip_bfloat16*, const __hip_bfloat16*, const __hip_bfloat16*,
                      __hip_bfloat16*, float*, int, int, int, float, hipStream_t);
 void launch_fmha_bwd_pre(const __hip_bfloat16*, const __hip_bfloat16*, float*, long, int,
@@ -1046,11 +1051,16 @@ torch::Tensor multi_tensor_l2norm_sq(std::vector<torch::Tensor> g) {
   return out;
 }
 
-// ------------------------------ fp8 forward -----------------------------
+// ------------------------- fp8 forward and backward ---------------------
 
-// bf16 [M,K] -> (e4m3fn bytes [M,K] as uint8, fp32 power-of-two scales [M]).
-std::vector<torch::Tensor> fp8_quant_rows(torch::Tensor x) {
+#define CHECK_FP8_FMT(fmt, who) \
+  TORCH_CHECK((fmt) == FP8_FMT_E4M3 || (fmt) == FP8_FMT_E5M2, who ": format must be 0 (e4m3) or 1 (e5m2)")
+
+// bf16 [M,K] -> (fp8 bytes [M,K] as uint8, fp32 power-of-two scales [M]).
+// fmt: FP8_FMT_E4M3 (0, default) or FP8_FMT_E5M2 (1).
+std::vector<torch::Tensor> fp8_quant_rows(torch::Tensor x, int64_t fmt) {
   CHECK_INPUT(x);
+  CHECK_FP8_FMT(fmt, "fp8_quant_rows");
   TORCH_CHECK(x.scalar_type() == at::ScalarType::BFloat16, "fp8_quant_rows: x must be bf16");
   TORCH_CHECK(x.dim() == 2, "fp8_quant_rows: x must be [M, K]");
   const long M = x.size(0);
@@ -1061,19 +1071,75 @@ std::vector<torch::Tensor> fp8_quant_rows(torch::Tensor x) {
   auto q = torch::empty({M, K}, x.options().dtype(torch::kUInt8));
   auto scale = torch::empty({M}, x.options().dtype(torch::kFloat));
   launch_fp8_quant_rows((const __hip_bfloat16*)x.data_ptr(), q.data_ptr<uint8_t>(),
-                        scale.data_ptr<float>(), M, (int)K, current_stream());
+                        scale.data_ptr<float>(), M, (int)K, (int)fmt, current_stream());
   return {q, scale};
 }
 
-// y[M,N] = bf16((xq . wq^T) * sx[m] * sw[n] + bias[n]); xq [M,K], wq [N,K] e4m3fn bytes.
+// bf16 [R,C] -> (fp8 bytes [C,Rp] as uint8 with Rp = ceil(R/128)*128 and zero
+// pad, fp32 scales [C], fp32 column sums [C] or an empty tensor).
+std::vector<torch::Tensor> fp8_quant_cols_t(torch::Tensor x, int64_t fmt, bool colsum) {
+  CHECK_INPUT(x);
+  CHECK_FP8_FMT(fmt, "fp8_quant_cols_t");
+  TORCH_CHECK(x.scalar_type() == at::ScalarType::BFloat16, "fp8_quant_cols_t: x must be bf16");
+  TORCH_CHECK(x.dim() == 2, "fp8_quant_cols_t: x must be [R, C]");
+  const long R = x.size(0);
+  const long C = x.size(1);
+  TORCH_CHECK(R >= 1, "fp8_quant_cols_t: R must be at least 1");
+  TORCH_CHECK(C > 0 && C % FP8_QUANT_VEC == 0 && C <= 65535L * FP8_COLS_TC,
+              "fp8_quant_cols_t: C must be a positive multiple of ", FP8_QUANT_VEC);
+  TORCH_CHECK((R + FP8_COLS_TR - 1) / FP8_COLS_TR <= INT_MAX, "fp8_quant_cols_t: R too large");
+  TORCH_CHECK((uintptr_t)x.data_ptr() % 16 == 0, "fp8_quant_cols_t: x must be 16-byte aligned");
+  const long Rp = (R + FP8_COLS_TR - 1) / FP8_COLS_TR * FP8_COLS_TR;
+  const int np = fp8_cols_partials(R, (int)C);
+  auto fopt = x.options().dtype(torch::kFloat);
+  auto q = torch::empty({C, Rp}, x.options().dtype(torch::kUInt8));
+  auto scale = torch::empty({C}, fopt);
+  auto sums = torch::empty({colsum ? C : 0}, fopt);
+  auto part = torch::empty({colsum ? 2 : 1, (long)np, C}, fopt);
+  float* part_amax = part.data_ptr<float>();
+  launch_fp8_quant_cols_t((const __hip_bfloat16*)x.data_ptr(), q.data_ptr<uint8_t>(),
+                          scale.data_ptr<float>(), colsum ? sums.data_ptr<float>() : nullptr,
+                          part_amax, colsum ? part_amax + (long)np * C : nullptr, R, (int)C,
+                          (int)fmt, current_stream());
+  return {q, scale, sums};
+}
+
+// fp32 column sums [C] of bf16 [R,C], by pass 1 of the column quantiser alone
+// (the bias gradient when no weight gradient is wanted).
+torch::Tensor fp8_colsum(torch::Tensor x) {
+  CHECK_INPUT(x);
+  TORCH_CHECK(x.scalar_type() == at::ScalarType::BFloat16, "fp8_colsum: x must be bf16");
+  TORCH_CHECK(x.dim() == 2, "fp8_colsum: x must be [R, C]");
+  const long R = x.size(0);
+  const long C = x.size(1);
+  TORCH_CHECK(R >= 1, "fp8_colsum: R must be at least 1");
+  TORCH_CHECK(C > 0 && C % FP8_QUANT_VEC == 0 && C <= 65535L * FP8_COLS_TC,
+              "fp8_colsum: C must be a positive multiple of ", FP8_QUANT_VEC);
+  TORCH_CHECK((uintptr_t)x.data_ptr() % 16 == 0, "fp8_colsum: x must be 16-byte aligned");
+  const int np = fp8_cols_partials(R, (int)C);
+  auto fopt = x.options().dtype(torch::kFloat);
+  auto sums = torch::empty({C}, fopt);
+  auto part = torch::empty({2, (long)np, C}, fopt);
+  float* part_amax = part.data_ptr<float>();
+  launch_fp8_quant_cols_t((const __hip_bfloat16*)x.data_ptr(), nullptr, nullptr,
+                          sums.data_ptr<float>(), part_amax, part_amax + (long)np * C, R, (int)C,
+                          FP8_FMT_E4M3, current_stream());
+  return sums;
+}
+
+// y[M,N] = bf16((xq . wq^T) * sx[m] * sw[n] + bias[n]); xq [M,K] fp8 bytes of format
+// fmt_x (e4m3 by default; e5m2 for the backward GEMMs, without bias), wq [N,K] e4m3fn bytes.
 torch::Tensor fp8_gemm_nt(torch::Tensor xq, torch::Tensor sx, torch::Tensor wq,
-                          torch::Tensor sw, c10::optional<torch::Tensor> bias) {
+                          torch::Tensor sw, c10::optional<torch::Tensor> bias, int64_t fmt_x) {
   CHECK_INPUT(xq);
+  CHECK_FP8_FMT(fmt_x, "fp8_gemm_nt");
+  TORCH_CHECK(fmt_x == FP8_FMT_E4M3 || !(bias.has_value() && bias->defined()),
+              "fp8_gemm_nt: no bias with an e5m2 first operand");
   CHECK_INPUT(sx);
   CHECK_INPUT(wq);
   CHECK_INPUT(sw);
   TORCH_CHECK(xq.scalar_type() == at::ScalarType::Byte && wq.scalar_type() == at::ScalarType::Byte,
-              "fp8_gemm_nt: operands are e4m3fn bytes viewed as uint8");
+              "fp8_gemm_nt: operands are fp8 bytes viewed as uint8");
   TORCH_CHECK(sx.scalar_type() == at::ScalarType::Float && sw.scalar_type() == at::ScalarType::Float,
               "fp8_gemm_nt: scales must be fp32");
   TORCH_CHECK(xq.dim() == 2 && wq.dim() == 2 && xq.size(1) == wq.size(1),
@@ -1102,21 +1168,24 @@ torch::Tensor fp8_gemm_nt(torch::Tensor xq, torch::Tensor sx, torch::Tensor wq,
   auto y = torch::empty({M, N}, xq.options().dtype(torch::kBFloat16));
   launch_fp8_gemm_nt(xq.data_ptr<uint8_t>(), sx.data_ptr<float>(), wq.data_ptr<uint8_t>(),
                      sw.data_ptr<float>(), bias_ptr, (__hip_bfloat16*)y.data_ptr(), M, (int)N,
-                     (int)K, current_stream());
+                     (int)K, (int)fmt_x, current_stream());
   return y;
 }
 
-// One-wave lane-map probe: c[16,16] = a[16,128] . bt[16,128]^T on e4m3fn bytes.
-torch::Tensor probe_mfma_fp8(torch::Tensor a, torch::Tensor bt) {
+// One-wave lane-map probe: c[16,16] = a[16,128] . bt[16,128]^T on fp8 bytes of
+// formats fmt_a and fmt_b (e4m3 by default).
+torch::Tensor probe_mfma_fp8(torch::Tensor a, torch::Tensor bt, int64_t fmt_a, int64_t fmt_b) {
   CHECK_INPUT(a);
   CHECK_INPUT(bt);
+  CHECK_FP8_FMT(fmt_a, "probe_mfma_fp8");
+  CHECK_FP8_FMT(fmt_b, "probe_mfma_fp8");
   TORCH_CHECK(a.scalar_type() == at::ScalarType::Byte && bt.scalar_type() == at::ScalarType::Byte);
   TORCH_CHECK(a.dim() == 2 && a.size(0) == 16 && a.size(1) == FP8_GEMM_BK &&
                   bt.dim() == 2 && bt.size(0) == 16 && bt.size(1) == FP8_GEMM_BK,
               "probe_mfma_fp8: a and bt must be [16, ", FP8_GEMM_BK, "]");
   auto c = torch::empty({16, 16}, a.options().dtype(torch::kFloat));
   launch_probe_mfma_fp8(a.data_ptr<uint8_t>(), bt.data_ptr<uint8_t>(), c.data_ptr<float>(),
-                        current_stream());
+                        (int)fmt_a, (int)fmt_b, current_stream());
   return c;
 }
 
@@ -1157,9 +1226,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("swiglu_bwd", &swiglu_bwd);
   mod.def("rope_fwd", &rope_fwd);
   mod.def("probe_mfma", &probe_mfma);
-  mod.def("fp8_quant_rows", &fp8_quant_rows);
-  mod.def("fp8_gemm_nt", &fp8_gemm_nt);
-  mod.def("probe_mfma_fp8", &probe_mfma_fp8);
+  mod.def("fp8_quant_rows", &fp8_quant_rows, py::arg("x"), py::arg("fmt") = FP8_FMT_E4M3);
+  mod.def("fp8_quant_cols_t", &fp8_quant_cols_t, py::arg("x"), py::arg("fmt") = FP8_FMT_E4M3,
+          py::arg("colsum") = false);
+  mod.def("fp8_colsum", &fp8_colsum, py::arg("x"));
+  mod.def("fp8_gemm_nt", &fp8_gemm_nt, py::arg("xq"), py::arg("sx"), py::arg("wq"), py::arg("sw"),
+          py::arg("bias"), py::arg("fmt_x") = FP8_FMT_E4M3);
+  mod.def("probe_mfma_fp8", &probe_mfma_fp8, py::arg("a"), py::arg("bt"),
+          py::arg("fmt_a") = FP8_FMT_E4M3, py::arg("fmt_b") = FP8_FMT_E4M3);
   mod.def("patch_embed_fwd", &patch_embed_fwd);
   mod.def("dino_ce_fwd", &dino_ce_fwd);
   mod.def("dino_ce_bwd", &dino_ce_bwd);

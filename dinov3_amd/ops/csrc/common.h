@@ -212,6 +212,17 @@ static inline void launch_colreduce_finalize(const float* part0, T* out0, const 
 #define FP8_GEMM_N_ALIGN 16   // N must be a multiple of one MFMA tile
 #define FP8_QUANT_VEC 8       // bf16 elements per 16-byte quantiser load
 
+// Operand formats; the values are the cbsz / blgp immediates of the scaled MFMA.
+#define FP8_FMT_E4M3 0
+#define FP8_FMT_E5M2 1
+
+// ---- FP8 transposing column quantiser (fp8_gemm.hip) ----
+#define FP8_COLS_THREADS 256
+#define FP8_COLS_TC 64             // columns per block, both passes (8 threads x 8 columns)
+#define FP8_COLS_TR 128            // rows per pass-2 tile = row padding unit = FP8_GEMM_BK
+#define FP8_COLS_SLICES 32         // pass 1: row slices per block
+#define FP8_COLS_MAX_PARTIALS 256  // pass 1: partial rows of the [partials, C] workspace
+
 #define HIP_CHECK_LAUNCH()                                                    \
   do {                                                                        \
     hipError_t e = hipGetLastError();                                         \

@@ -16,7 +16,7 @@ import torch
 import torch.nn as nn
 
 from ..layers.dino_head import DINOHead
-from ..layers.fp8_linear import convert_linears_to_fp8, fp8_env_enabled
+from ..layers.fp8_linear import convert_linears_to_fp8, fp8_bwd_env_enabled, fp8_env_enabled
 from ..loss import DINOLoss, GramLoss, KoLeoLoss, KoLeoLossDistributed, iBOTPatchLoss
 from ..models import build_model_from_cfg
 from ..ops import ema_update_
@@ -158,13 +158,20 @@ class SSLMetaArch(nn.Module):
         # FP8 forward for the block linears of both towers (what the reference
         # intended: init_fp8 on teacher and student, commented out in
         # dinov3_jax/models/__init__.py:42,53). Heads, patch embed and the gram
-        # teacher stay bf16; backward stays bf16. DINOV3_FP8=1 switches it on
-        # without a config change (for timing the stock benchmark).
+        # teacher stay bf16. DINOV3_FP8=1 switches it on without a config
+        # change (for timing the stock benchmark). student.fp8_backward /
+        # DINOV3_FP8_BWD=1 additionally run dgrad and wgrad of the student's
+        # block linears in fp8 (the teacher takes no gradients).
         self.fp8_enabled = bool(config.student.fp8_enabled) or fp8_env_enabled()
+        want_fp8_bwd = bool(config.student.get("fp8_backward", False)) or fp8_bwd_env_enabled()
+        self.fp8_backward = want_fp8_bwd and self.fp8_enabled
+        if want_fp8_bwd and not self.fp8_enabled:
+            logger.warning("fp8 backward requested (student.fp8_backward / DINOV3_FP8_BWD) "
+                           "without the fp8 forward (student.fp8_enabled / DINOV3_FP8): ignored")
         if self.fp8_enabled:
             fp8_filter = config.student.get("fp8_filter", "blocks") or "blocks"
-            for backbone in (self.student_backbone, self.teacher_backbone):
-                convert_linears_to_fp8(backbone, fp8_filter)
+            convert_linears_to_fp8(self.student_backbone, fp8_filter, backward=self.fp8_backward)
+            convert_linears_to_fp8(self.teacher_backbone, fp8_filter)
 
     # ------------------------------------------------------------------
     def _weight_schedule(self, sched_cfg):
