@@ -126,10 +126,24 @@ class SelfAttentionBlock(nn.Module):
               and not isinstance(self.mlp.drop, nn.Dropout))
         return fa, fm
 
+    def _gather_norm_ok(self, norm, flat: torch.Tensor, inplace_ok: bool) -> bool:
+        """Drop-path gather + LayerNorm through one node (ops/gather_norm.py):
+        only where the fused residual scatter may mutate `flat` in place, for
+        the project's LayerNorm at a width the kernels cover. The node hands
+        `flat` on as a second output, which autograd allows neither for a
+        leaf that requires grad nor for a view."""
+        from ..ops.gather_norm import fused_gather_norm_enabled, gather_norm_supported
+        from .norms import LayerNorm
+
+        return (inplace_ok and type(norm) is LayerNorm
+                and gather_norm_supported(flat.shape[-1])
+                and not (flat.requires_grad and (flat.is_leaf or flat._is_view()))
+                and fused_gather_norm_enabled(flat))
+
     # ------------------------------------------------------------------
     def forward_flat(self, flat: torch.Tensor, metas: List[GroupMeta],
                      plan: Optional[DropPathPlan] = None, block_idx: int = 0,
-                     inplace_ok: bool = True) -> torch.Tensor:
+                     inplace_ok: bool = True, grad_owner=None) -> torch.Tensor:
         fa, fm = self._fusable()
         if not (self.training and self.sample_drop_ratio > 0.0):
             if fa:
@@ -156,14 +170,26 @@ class SelfAttentionBlock(nn.Module):
             rows1, metas1, scale1 = plan.take(2 * block_idx)
         else:
             rows1, metas1, scale1 = _subset_rows(metas, keep_ratio, flat.device)
-        sub = gather_rows(flat, rows1)
-        if fa:
+        # decided once, on the buffer that came in: both sublayers or neither
+        gn1 = fa and self._gather_norm_ok(self.norm1, flat, inplace_ok)
+        gn2 = fm and self._gather_norm_ok(self.norm2, flat, inplace_ok)
+        if gn1:
+            from ..ops.gather_norm import gather_layer_norm
+
+            flat, n = gather_layer_norm(flat, rows1, self.norm1.weight, self.norm1.bias,
+                                        self.norm1.eps, grad_owner)
+            res = self.attn.forward_flat(n, metas1, skip_proj_bias=True)
+            flat = ls_scatter_add_rows(flat, rows1, res, self.ls1.gamma,
+                                       self.attn.proj.bias, scale1)
+        elif fa:
+            sub = gather_rows(flat, rows1)
             if not inplace_ok:
                 flat = flat.clone()
             res = self.attn.forward_flat(self.norm1(sub), metas1, skip_proj_bias=True)
             flat = ls_scatter_add_rows(flat, rows1, res, self.ls1.gamma,
                                        self.attn.proj.bias, scale1)
         else:
+            sub = gather_rows(flat, rows1)
             res = self.ls1(self.attn.forward_flat(self.norm1(sub), metas1))
             flat = scatter_add_rows(flat, rows1, res, scale1)
 
@@ -171,6 +197,14 @@ class SelfAttentionBlock(nn.Module):
             rows2, _, scale2 = plan.take(2 * block_idx + 1)
         else:
             rows2, _, scale2 = _subset_rows(metas, keep_ratio, flat.device)
+        if gn2:
+            from ..ops.gather_norm import gather_layer_norm
+
+            flat, n = gather_layer_norm(flat, rows2, self.norm2.weight, self.norm2.bias,
+                                        self.norm2.eps, grad_owner)
+            res = self.mlp(n, skip_out_bias=True)
+            return ls_scatter_add_rows(flat, rows2, res, self.ls2.gamma,
+                                       self.mlp.fc2.bias, scale2)
         sub = gather_rows(flat, rows2)
         if fm:
             res = self.mlp(self.norm2(sub), skip_out_bias=True)

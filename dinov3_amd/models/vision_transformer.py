@@ -210,12 +210,24 @@ class DinoVisionTransformer(nn.Module):
                 flat = checkpoint(block.forward_flat, flat, metas, plan, i, False,
                                   use_reentrant=False)
         else:
+            # With drop path the blocks accumulate their LayerNorm gradients
+            # straight into the residual-stream gradient (ops/gather_norm.py);
+            # the node after the last block makes that buffer the stack's own.
+            owner = None
+            if plan is not None and torch.is_grad_enabled() and flat.requires_grad:
+                from ..ops.gather_norm import (GradOwner, fused_gather_norm_enabled,
+                                               own_residual_grad)
+
+                if fused_gather_norm_enabled(flat):
+                    owner = GradOwner()
             for i, block in enumerate(self.blocks):
-                flat = block.forward_flat(flat, metas, plan, i)
+                flat = block.forward_flat(flat, metas, plan, i, grad_owner=owner)
                 if _NAN_CHECK and not torch.isfinite(flat).all():
                     raise FloatingPointError(
                         f"non-finite activations after block {i} "
                         f"(DINOV3_NAN_CHECK sanitizer)")
+            if owner is not None:
+                flat = own_residual_grad(flat, owner)
         tokens = uncat_with_shapes(flat, shapes, counts)
 
         output = []

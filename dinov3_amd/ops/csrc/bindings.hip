@@ -21,6 +21,13 @@ template <typename T>
 void launch_layernorm_bwd(const T*, const T*, const T*, const float*, const float*, T*,
                           float*, T*, T*, long, int, hipStream_t);
 template <typename T>
+void launch_gather_layernorm_fwd(const T*, const long*, const T*, const T*, T*, T*, float*,
+                                 float*, long, int, float, hipStream_t);
+template <typename T>
+void launch_layernorm_bwd_scatter_acc(const T*, const T*, const T*, const float*,
+                                      const float*, T*, const long*, float*, T*, T*, long,
+                                      int, hipStream_t);
+template <typename T>
 void launch_rmsnorm_fwd(const T*, const T*, T*, float*, long, int, float, hipStream_t);
 template <typename T>
 void launch_rmsnorm_bwd(const T*, const T*, const T*, const float*, T*, float*, T*, long,
@@ -220,6 +227,78 @@ std::vector<torch::Tensor> layernorm_bwd(torch::Tensor dy, torch::Tensor x, torc
         (scalar_t*)db.data_ptr(), rows, D, current_stream());
   });
   return {dx, dw, db};
+}
+
+// LayerNorm of the rows flat[idx]: (y, sub = flat[idx], mean, rstd), bit-equal
+// to row_gather + layernorm_fwd with one pass less over the gathered rows.
+std::vector<torch::Tensor> gather_layernorm_fwd(torch::Tensor flat, torch::Tensor idx,
+                                                torch::Tensor w, torch::Tensor b, double eps) {
+  CHECK_INPUT(flat);
+  CHECK_INPUT(idx);
+  CHECK_INPUT(w);
+  CHECK_INPUT(b);
+  TORCH_CHECK(flat.dim() == 2, "gather_layernorm_fwd: flat must be [R, D]");
+  TORCH_CHECK(idx.scalar_type() == torch::kLong, "gather_layernorm_fwd: idx must be int64");
+  const int D = flat.size(1);
+  TORCH_CHECK(D % 8 == 0, "gather_layernorm_fwd needs D % 8 == 0");
+  TORCH_CHECK(w.numel() == D && b.numel() == D && w.scalar_type() == flat.scalar_type() &&
+                  b.scalar_type() == flat.scalar_type(),
+              "gather_layernorm_fwd: w / b must be [D] of flat's dtype");
+  const long M = idx.numel();
+  auto y = torch::empty({M, D}, flat.options());
+  auto sub = torch::empty({M, D}, flat.options());
+  auto mean = torch::empty({M}, flat.options().dtype(torch::kFloat));
+  auto rstd = torch::empty({M}, flat.options().dtype(torch::kFloat));
+  if (M == 0) return {y, sub, mean, rstd};
+  DISPATCH_FLOAT_BF16(flat.scalar_type(), "gather_layernorm_fwd", [&] {
+    launch_gather_layernorm_fwd<scalar_t>(
+        (const scalar_t*)flat.data_ptr(), idx.data_ptr<long>(), (const scalar_t*)w.data_ptr(),
+        (const scalar_t*)b.data_ptr(), (scalar_t*)y.data_ptr(), (scalar_t*)sub.data_ptr(),
+        mean.data_ptr<float>(), rstd.data_ptr<float>(), M, D, (float)eps, current_stream());
+  });
+  return {y, sub, mean, rstd};
+}
+
+// LayerNorm backward whose dx rows are accumulated into dacc[idx] in place
+// (rows of idx disjoint); returns (dw, db), bit-equal to layernorm_bwd's.
+std::vector<torch::Tensor> layernorm_bwd_scatter_acc_(torch::Tensor dacc, torch::Tensor idx,
+                                                      torch::Tensor dy, torch::Tensor x,
+                                                      torch::Tensor w, torch::Tensor mean,
+                                                      torch::Tensor rstd) {
+  CHECK_INPUT(dacc);
+  CHECK_INPUT(idx);
+  CHECK_INPUT(dy);
+  CHECK_INPUT(x);
+  CHECK_INPUT(w);
+  CHECK_INPUT(mean);
+  CHECK_INPUT(rstd);
+  TORCH_CHECK(dacc.dim() == 2 && x.dim() == 2 && dy.dim() == 2,
+              "layernorm_bwd_scatter_acc_: dacc, dy, x must be 2-D");
+  TORCH_CHECK(idx.scalar_type() == torch::kLong,
+              "layernorm_bwd_scatter_acc_: idx must be int64");
+  const int D = x.size(1);
+  const long M = x.size(0);
+  TORCH_CHECK(D % 8 == 0 && D <= 1536,
+              "layernorm_bwd_scatter_acc_ supports D % 8 == 0 and D <= 1536, got ", D);
+  TORCH_CHECK(dacc.size(1) == D && dy.size(0) == M && dy.size(1) == D && idx.numel() == M &&
+                  mean.numel() == M && rstd.numel() == M && w.numel() == D,
+              "layernorm_bwd_scatter_acc_: shape mismatch");
+  TORCH_CHECK(dacc.scalar_type() == x.scalar_type() && dy.scalar_type() == x.scalar_type() &&
+                  w.scalar_type() == x.scalar_type() &&
+                  mean.scalar_type() == torch::kFloat && rstd.scalar_type() == torch::kFloat,
+              "layernorm_bwd_scatter_acc_: dtype mismatch");
+  if (M == 0) return {torch::zeros({D}, x.options()), torch::zeros({D}, x.options())};
+  auto dw = torch::empty({D}, x.options());
+  auto db = torch::empty({D}, x.options());
+  auto ws = colreduce_workspace(2, D, x);
+  DISPATCH_FLOAT_BF16(x.scalar_type(), "layernorm_bwd_scatter_acc_", [&] {
+    launch_layernorm_bwd_scatter_acc<scalar_t>(
+        (const scalar_t*)dy.data_ptr(), (const scalar_t*)x.data_ptr(),
+        (const scalar_t*)w.data_ptr(), mean.data_ptr<float>(), rstd.data_ptr<float>(),
+        (scalar_t*)dacc.data_ptr(), idx.data_ptr<long>(), ws.data_ptr<float>(),
+        (scalar_t*)dw.data_ptr(), (scalar_t*)db.data_ptr(), M, D, current_stream());
+  });
+  return {dw, db};
 }
 
 std::vector<torch::Tensor> rmsnorm_fwd(torch::Tensor x, torch::Tensor w, double eps) {
@@ -1207,6 +1286,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("blaslt_probe_epilogue", &blaslt_probe_epilogue);
   mod.def("layernorm_fwd", &layernorm_fwd);
   mod.def("layernorm_bwd", &layernorm_bwd);
+  mod.def("gather_layernorm_fwd", &gather_layernorm_fwd);
+  mod.def("layernorm_bwd_scatter_acc_", &layernorm_bwd_scatter_acc_);
   mod.def("rmsnorm_fwd", &rmsnorm_fwd);
   mod.def("rmsnorm_bwd", &rmsnorm_bwd);
   mod.def("l2norm_fwd", &l2norm_fwd);

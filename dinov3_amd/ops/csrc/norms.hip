@@ -47,15 +47,22 @@ DEV_INLINE void row_store8(T* p, int i, const float* in) {
 
 // ------------------------------ LayerNorm ------------------------------
 
-template <typename T, bool V8>
+// GATHER: row r of the problem is x[idx[r]] (drop-path subset of the flat
+// residual buffer); the second pass also writes the compact copy sub[r] that
+// backward reads, so the gathered rows cross HBM once. Same block size, loops
+// and reduction order as the plain kernel: y / mean / rstd are bit-equal to
+// row_gather followed by layernorm_fwd.
+template <typename T, bool V8, bool GATHER = false>
 __global__ void layernorm_fwd_kernel(
     const T* __restrict__ x, const T* __restrict__ w, const T* __restrict__ b,
     T* __restrict__ y, float* __restrict__ mean_out, float* __restrict__ rstd_out,
-    long rows, int D, float eps) {
+    long rows, int D, float eps, const long* __restrict__ idx = nullptr,
+    T* __restrict__ sub = nullptr) {
+  static_assert(V8 || !GATHER, "the gathered forward is 8-wide only");
   constexpr int EW = V8 ? 8 : 1;
   __shared__ float red[16];
   for (long row = blockIdx.x; row < rows; row += gridDim.x) {
-    const T* xr = x + row * (long)D;
+    const T* xr = x + (GATHER ? idx[row] : row) * (long)D;
     T* yr = y + row * (long)D;
     float s = 0.f, s2 = 0.f;
     ROW_LOOP(i) {
@@ -79,7 +86,15 @@ __global__ void layernorm_fwd_kernel(
     }
     ROW_LOOP(i) {
       float v[EW], wv[EW], bv[EW], o[EW];
-      row_load8<T, V8>(xr, i, v);
+      if constexpr (GATHER) {
+        T raw[8];
+        Vec8<T>::load(raw, xr + i);
+        Vec8<T>::store(sub + row * (long)D + i, raw);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = ScalarOps<T>::load(raw + e);
+      } else {
+        row_load8<T, V8>(xr, i, v);
+      }
       row_load8<T, V8>(w, i, wv);
       row_load8<T, V8>(b, i, bv);
 #pragma unroll
@@ -154,6 +169,19 @@ __global__ void layernorm_bwd_kernel(
   }
 }
 
+// dx of one element of the wave-per-row backward,
+//   (g * w - (sum_dyw + xhat * sum_dyw_xhat) / D) * rstd,
+// with the fused multiply-adds spelled out: left to the compiler, the plain
+// and the accumulating instantiation of one width contracted it differently
+// and their dx differed in the last bit. This is the form the compiler chose
+// for D = 1024 and 1536.
+DEV_INLINE float ln_dx(float g, float w, float xhat, float sum_dyw, float sum_dyw_xhat,
+                       float inv_d, float r) {
+#pragma clang fp contract(off)
+  const float s = __builtin_fmaf(sum_dyw_xhat, xhat, sum_dyw);
+  return __builtin_fmaf(g, w, -(s * inv_d)) * r;
+}
+
 // Wave-per-row LayerNorm backward: each 64-lane wave owns a row, the row's
 // dy/x values stay register-cached between the reduction and the dx pass
 // (ONE read of dy and x instead of two), and the row loop has no block
@@ -163,12 +191,23 @@ __global__ void layernorm_bwd_kernel(
 // one cross-wave merge at block end, one accumulator at a time, after which
 // the block stores its partial row. CHUNKS = ceil(D/512) (1: D<=512, 2: 1024,
 // 3: 1536).
-template <typename T, int CHUNKS>
-__global__ __launch_bounds__(256) void layernorm_bwd_wave_kernel(
+// SCATTER: `dx` is a gradient accumulator of the buffer the rows were
+// gathered from; the last phase does dx[idx[row]] += dx_row (fp32 add, one
+// rounding) instead of storing the row to its own buffer. idx rows are
+// disjoint, so the read-modify-write needs no atomics. Row->wave assignment,
+// grid and the dgamma/dbeta reduction do not depend on the flag.
+// The accumulator loads cost registers; the SCATTER form is held to the plain
+// kernel's occupancy at D = 1024 and 1536 (4 and 3 waves per SIMD) through
+// the second launch bound, which is 1 (no constraint) for the plain kernel
+// and for fp32 I/O, where holding it would spill.
+template <typename T, int CHUNKS, bool SCATTER = false>
+__global__ __launch_bounds__(256, SCATTER && sizeof(T) == 2
+                                      ? (CHUNKS == 1 ? 5 : CHUNKS == 2 ? 4 : 3) : 1)
+void layernorm_bwd_wave_kernel(
     const T* __restrict__ dy, const T* __restrict__ x, const T* __restrict__ w,
     const float* __restrict__ mean, const float* __restrict__ rstd,
     T* __restrict__ dx, float* __restrict__ dw_ws, float* __restrict__ db_ws,
-    long rows, int D) {
+    long rows, int D, const long* __restrict__ idx = nullptr) {
   constexpr int NW = 4;  // waves per 256-thread block
   const int wid = threadIdx.x / 64;
   const int lane = threadIdx.x & 63;
@@ -220,7 +259,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_wave_kernel(
       sum_dyw += __shfl_xor(sum_dyw, off, 64);
       sum_dyw_xhat += __shfl_xor(sum_dyw_xhat, off, 64);
     }
-    T* dxr = dx + row * (long)D;
+    T* dxr = dx + (SCATTER ? idx[row] : row) * (long)D;
 #pragma unroll
     for (int c = 0; c < CHUNKS; ++c) {
       const int i = (c * 64 + lane) * 8;
@@ -228,7 +267,13 @@ __global__ __launch_bounds__(256) void layernorm_bwd_wave_kernel(
         float o[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e)
-          o[e] = (g[c][e] * wv[c][e] - (sum_dyw + xhat[c][e] * sum_dyw_xhat) * inv_d) * r;
+          o[e] = ln_dx(g[c][e], wv[c][e], xhat[c][e], sum_dyw, sum_dyw_xhat, inv_d, r);
+        if constexpr (SCATTER) {
+          float acc[8];
+          row_load8<T, true>(dxr, i, acc);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) o[e] += acc[e];
+        }
         row_store8<T, true>(dxr, i, o);
       }
     }
@@ -425,6 +470,58 @@ void launch_layernorm_fwd(const T* x, const T* w, const T* b, T* y, float* mean,
                                      rows, D, eps));
 }
 
+// y[r] = LayerNorm(flat[idx[r]]) and sub[r] = flat[idx[r]] in one kernel
+// (D % 8 == 0). Grid and block are those of launch_layernorm_fwd.
+template <typename T>
+void launch_gather_layernorm_fwd(const T* flat, const long* idx, const T* w, const T* b,
+                                 T* y, T* sub, float* mean, float* rstd, long rows, int D,
+                                 float eps, hipStream_t stream) {
+  int grid = (int)min(rows, (long)8192);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(layernorm_fwd_kernel<T, true, true>), dim3(grid),
+                     dim3(norm_block_for(D)), 0, stream, flat, w, b, y, mean, rstd, rows, D,
+                     eps, idx, sub);
+}
+
+// The wave-per-row backward. SCATTER = false stores dx[row]; SCATTER = true
+// accumulates the row into dx[idx[row]]. Returns the grid (= partial rows).
+template <typename T, bool SCATTER>
+static int launch_layernorm_bwd_wave(const T* dy, const T* x, const T* w, const float* mean,
+                                     const float* rstd, T* dx, const long* idx, float* dw_ws,
+                                     float* db_ws, long rows, int D, hipStream_t stream) {
+  // One read of dy/x, no block barriers in the row loop. Four blocks per CU
+  // (four waves per SIMD at the 120 VGPRs of D = 1024; three at the 166
+  // VGPRs of D = 1536), every block the same number of row rounds.
+  const int grid =
+      even_row_grid((rows + 3) / 4, D <= 1024 ? LN_BWD_GRID : LN_BWD_GRID * 3 / 4);
+  const size_t shmem = 4 * (size_t)D * sizeof(float);
+  if (D <= 512)
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(layernorm_bwd_wave_kernel<T, 1, SCATTER>), dim3(grid),
+                       dim3(256), shmem, stream, dy, x, w, mean, rstd, dx, dw_ws, db_ws,
+                       rows, D, idx);
+  else if (D <= 1024)
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(layernorm_bwd_wave_kernel<T, 2, SCATTER>), dim3(grid),
+                       dim3(256), shmem, stream, dy, x, w, mean, rstd, dx, dw_ws, db_ws,
+                       rows, D, idx);
+  else
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(layernorm_bwd_wave_kernel<T, 3, SCATTER>), dim3(grid),
+                       dim3(256), shmem, stream, dy, x, w, mean, rstd, dx, dw_ws, db_ws,
+                       rows, D, idx);
+  return grid;
+}
+
+// dacc[idx[r]] += dx[r] of the LayerNorm backward; wave kernel widths only
+// (D % 8 == 0, D <= 1536 — the caller checks). dw / db / ws as below.
+template <typename T>
+void launch_layernorm_bwd_scatter_acc(const T* dy, const T* x, const T* w, const float* mean,
+                                      const float* rstd, T* dacc, const long* idx, float* ws,
+                                      T* dw, T* db, long rows, int D, hipStream_t stream) {
+  float* dw_ws = ws;
+  float* db_ws = ws + (long)COLRED_MAX_PARTIALS * D;
+  const int grid = launch_layernorm_bwd_wave<T, true>(dy, x, w, mean, rstd, dacc, idx, dw_ws,
+                                                      db_ws, rows, D, stream);
+  launch_colreduce_finalize<T>(dw_ws, dw, db_ws, db, grid, D, stream);
+}
+
 // dw / db come out in T; `ws` is an fp32 workspace of 2 * COLRED_MAX_PARTIALS
 // rows of D (dgamma partials, then dbeta partials).
 template <typename T>
@@ -435,24 +532,8 @@ void launch_layernorm_bwd(const T* dy, const T* x, const T* w, const float* mean
   float* db_ws = ws + (long)COLRED_MAX_PARTIALS * D;
   int grid;
   if (D % 8 == 0 && D <= 1536) {
-    // wave-per-row: one read of dy/x, no block barriers in the row loop.
-    // Four blocks per CU (four waves per SIMD at the 120 VGPRs of D = 1024;
-    // three at the 166 VGPRs of D = 1536), every block the same number of
-    // row rounds.
-    grid = even_row_grid((rows + 3) / 4, D <= 1024 ? LN_BWD_GRID : LN_BWD_GRID * 3 / 4);
-    size_t shmem = 4 * (size_t)D * sizeof(float);
-    if (D <= 512)
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(layernorm_bwd_wave_kernel<T, 1>), dim3(grid),
-                         dim3(256), shmem, stream, dy, x, w, mean, rstd, dx, dw_ws, db_ws,
-                         rows, D);
-    else if (D <= 1024)
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(layernorm_bwd_wave_kernel<T, 2>), dim3(grid),
-                         dim3(256), shmem, stream, dy, x, w, mean, rstd, dx, dw_ws, db_ws,
-                         rows, D);
-    else
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(layernorm_bwd_wave_kernel<T, 3>), dim3(grid),
-                         dim3(256), shmem, stream, dy, x, w, mean, rstd, dx, dw_ws, db_ws,
-                         rows, D);
+    grid = launch_layernorm_bwd_wave<T, false>(dy, x, w, mean, rstd, dx, nullptr, dw_ws,
+                                               db_ws, rows, D, stream);
   } else {
     grid = even_row_grid(rows, LN_BWD_GRID);
     size_t shmem = (16 + 2 * (size_t)D) * sizeof(float);
@@ -507,6 +588,13 @@ void launch_l2norm_bwd(const T* dy, const T* y, const float* s, T* dx, long rows
   template void launch_layernorm_bwd<T>(const T*, const T*, const T*, const float*,       \
                                         const float*, T*, float*, T*, T*, long, int,      \
                                         hipStream_t);                                     \
+  template void launch_gather_layernorm_fwd<T>(const T*, const long*, const T*, const T*, \
+                                               T*, T*, float*, float*, long, int, float,  \
+                                               hipStream_t);                              \
+  template void launch_layernorm_bwd_scatter_acc<T>(const T*, const T*, const T*,         \
+                                                    const float*, const float*, T*,       \
+                                                    const long*, float*, T*, T*, long,    \
+                                                    int, hipStream_t);                    \
   template void launch_rmsnorm_fwd<T>(const T*, const T*, T*, float*, long, int, float,   \
                                       hipStream_t);                                       \
   template void launch_rmsnorm_bwd<T>(const T*, const T*, const T*, const float*, T*,     \

@@ -142,6 +142,41 @@ def main():
         timeit(lambda: ops.layernorm_bwd(dys, xs, wl, ln_mean, ln_rstd), it),
         timeit(ln_bwd_ref, it),
         3 * RS * D * 2)
+
+    # Drop-path gather fused into LayerNorm, and its backward fused into the
+    # residual-gradient accumulation. The second column is the UNFUSED
+    # sequence of this project's own ops, not torch: row_gather +
+    # layernorm_fwd, and layernorm_bwd + zero fill + row_scatter_add_ + the
+    # full-buffer add autograd performs. Bytes: the fused kernels' minimum
+    # (fwd: rows read once, y and the compact copy written; bwd: dy, x and the
+    # accumulator rows read, the accumulator rows written).
+    # RF: rows of the student's flat buffer in the flagship step.
+    RF = 44672
+    empty_f = torch.empty(0, device=dev)
+    xf = torch.randn(RF, D, device=dev).bfloat16()
+    dacc = torch.randn(RF, D, device=dev).bfloat16()
+    keep_f = torch.randperm(RF, device=dev)[:RS]
+    _, sub, g_mean, g_rstd = ops.gather_layernorm_fwd(xf, keep_f, wl, b, 1e-6)
+
+    def gather_ln_unfused():
+        return ops.layernorm_fwd(ops.row_gather(xf, keep_f), wl, b, 1e-6)
+
+    row(f"gather_layernorm_fwd [{RS} of {RF},1024]",
+        timeit(lambda: ops.gather_layernorm_fwd(xf, keep_f, wl, b, 1e-6), it),
+        timeit(gather_ln_unfused, it),
+        3 * RS * D * 2)
+
+    def ln_bwd_scatter_unfused():
+        dx, dw_, db_ = ops.layernorm_bwd(dys, sub, wl, g_mean, g_rstd)
+        buf = torch.zeros(RF, D, dtype=dx.dtype, device=dev)
+        ops.row_scatter_add_(buf, keep_f, dx, empty_f)
+        return dacc + buf, dw_, db_
+
+    row(f"ln_bwd_scatter_acc [{RS} of {RF},1024]",
+        timeit(lambda: ops.layernorm_bwd_scatter_acc_(dacc, keep_f, dys, sub, wl, g_mean,
+                                                      g_rstd), it),
+        timeit(ln_bwd_scatter_unfused, it),
+        4 * RS * D * 2)
     if args.streaming_only:
         return
 
