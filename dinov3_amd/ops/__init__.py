@@ -31,6 +31,7 @@ from .row_ops import gather_rows, scatter_add_rows
 from .flat_attention import flat_multi_fmha
 from .fp8_linear import (fp8_bwd_eligible, fp8_eligible, fp8_linear, fp8_quantize_cols_t,
                          fp8_quantize_rows)
+from .knn import knn_topk, knn_topk_ref
 
 __all__ = [
     "fp8_quantize_rows",
@@ -54,6 +55,8 @@ __all__ = [
     "gather_rows",
     "scatter_add_rows",
     "flat_multi_fmha",
+    "knn_topk",
+    "knn_topk_ref",
     "hip_ops",
     "has_hip_ops",
 ]

@@ -130,6 +130,9 @@ void launch_fp8_gemm_nt(const unsigned char*, const float*, const unsigned char*
                         hipStream_t);
 void launch_probe_mfma_fp8(const unsigned char*, const unsigned char*, float*, int, int,
                            hipStream_t);
+int knn_topk_auto_splits(long, long);
+void launch_knn_topk(const __hip_bfloat16*, const __hip_bfloat16*, unsigned long long*, float*,
+                     int*, long, long, int, int, int, hipStream_t);
 void launch_fmha_fwd(const __hip_bfloat16*, const __hip_bfloat16*, const __hip_bfloat16*,
                      __hip_bfloat16*, float*, int, int, int, float, hipStream_t);
 void launch_fmha_bwd_pre(const __hip_bfloat16*, const __hip_bfloat16*, float*, long, int,
@@ -1268,6 +1271,48 @@ torch::Tensor probe_mfma_fp8(torch::Tensor a, torch::Tensor bt, int64_t fmt_a, i
   return c;
 }
 
+// ------------------------------- k-NN -----------------------------------
+
+// (val [Q,k] fp32, idx [Q,k] int32): the k largest dot products of every row of
+// q [Q,D] with the rows of bank [N,D], ordered by (value descending, bank row
+// ascending). splits: slices of the bank along N; 0 lets the kernel choose.
+std::vector<torch::Tensor> knn_topk(torch::Tensor q, torch::Tensor bank, int64_t k,
+                                    int64_t splits) {
+  CHECK_INPUT(q);
+  CHECK_INPUT(bank);
+  TORCH_CHECK(q.scalar_type() == at::ScalarType::BFloat16 &&
+                  bank.scalar_type() == at::ScalarType::BFloat16,
+              "knn_topk: q and bank must be bf16");
+  TORCH_CHECK(q.dim() == 2 && bank.dim() == 2, "knn_topk: q must be [Q, D] and bank [N, D]");
+  TORCH_CHECK(q.device() == bank.device(), "knn_topk: q and bank must be on one device");
+  const long Q = q.size(0);
+  const long N = bank.size(0);
+  const long D = q.size(1);
+  TORCH_CHECK(bank.size(1) == D, "knn_topk: q and bank must share D, got ", D, " and ",
+              bank.size(1));
+  TORCH_CHECK(D > 0 && D % 32 == 0 && D <= INT_MAX, "knn_topk: D must be a positive multiple of 32");
+  TORCH_CHECK(N < (1L << 31), "knn_topk: N must be below 2^31");
+  TORCH_CHECK(k >= 1 && k <= 256 && k <= N, "knn_topk: need 1 <= k <= min(N, 256), got k = ", k,
+              " with N = ", N);
+  TORCH_CHECK(splits >= 0 && splits <= 1024, "knn_topk: splits must be in [0, 1024]");
+  TORCH_CHECK((uintptr_t)q.data_ptr() % 16 == 0 && (uintptr_t)bank.data_ptr() % 16 == 0,
+              "knn_topk: q and bank must be 16-byte aligned");
+  auto val = torch::empty({Q, (long)k}, q.options().dtype(torch::kFloat));
+  auto idx = torch::empty({Q, (long)k}, q.options().dtype(torch::kInt));
+  if (Q == 0) return {val, idx};
+  const int ns = splits > 0 ? (int)splits : knn_topk_auto_splits(Q, N);
+  torch::Tensor ws;
+  unsigned long long* ws_ptr = nullptr;
+  if (ns > 1) {
+    ws = torch::empty({(long)ns, Q, (long)k}, q.options().dtype(torch::kLong));
+    ws_ptr = (unsigned long long*)ws.data_ptr();
+  }
+  launch_knn_topk((const __hip_bfloat16*)q.data_ptr(), (const __hip_bfloat16*)bank.data_ptr(),
+                  ws_ptr, val.data_ptr<float>(), idx.data_ptr<int>(), Q, N, (int)D, (int)k, ns,
+                  current_stream());
+  return {val, idx};
+}
+
 }  // namespace
 
 // hipBLASLt fused-epilogue entry points (blaslt_ext.hip)
@@ -1329,6 +1374,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("dino_ce_fact_bwd", &dino_ce_fact_bwd);
   mod.def("sinkhorn_colsum", &sinkhorn_colsum);
   mod.def("sinkhorn_div_row", &sinkhorn_div_row);
+  mod.def("knn_topk", &knn_topk, py::arg("q"), py::arg("bank"), py::arg("k"),
+          py::arg("splits") = 0);
   mod.def("fmha_fwd", &fmha_fwd);
   mod.def("fmha_rope_fwd", [](torch::Tensor qkv, torch::Tensor sin_t, torch::Tensor cos_t,
                               int64_t prefix) {
