@@ -1,4 +1,5 @@
 from .knn import evaluate_knn, evaluate_knn_sharded, extract_features
-from .linear import evaluate_linear_probe
+from .linear import evaluate_linear_probe, evaluate_linear_sharded
 
-__all__ = ["extract_features", "evaluate_knn", "evaluate_knn_sharded", "evaluate_linear_probe"]
+__all__ = ["extract_features", "evaluate_knn", "evaluate_knn_sharded", "evaluate_linear_probe",
+           "evaluate_linear_sharded"]

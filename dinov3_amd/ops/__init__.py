@@ -32,8 +32,13 @@ from .flat_attention import flat_multi_fmha
 from .fp8_linear import (fp8_bwd_eligible, fp8_eligible, fp8_linear, fp8_quantize_cols_t,
                          fp8_quantize_rows)
 from .knn import knn_topk, knn_topk_ref
+from .linear_probe import probe_ce, probe_ce_ref, probe_sgd_, probe_sgd_ref_
 
 __all__ = [
+    "probe_ce",
+    "probe_ce_ref",
+    "probe_sgd_",
+    "probe_sgd_ref_",
     "fp8_quantize_rows",
     "fp8_quantize_cols_t",
     "fp8_bwd_eligible",

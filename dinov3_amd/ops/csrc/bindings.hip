@@ -130,6 +130,14 @@ void launch_fp8_gemm_nt(const unsigned char*, const float*, const unsigned char*
                         hipStream_t);
 void launch_probe_mfma_fp8(const unsigned char*, const unsigned char*, float*, int, int,
                            hipStream_t);
+int probe_ce_row_blocks(long, int, int);
+void probe_ce_layout(int, int, bool, int*, int*);
+template <typename T>
+void launch_probe_ce(T*, const float*, const long*, float*, float*, long, int, int, int, float,
+                     bool, int, hipStream_t);
+template <typename GT>
+void launch_probe_sgd(float*, float*, const GT*, const float*, const float*, __hip_bfloat16*, int,
+                      long, float, float, hipStream_t);
 int knn_topk_auto_splits(long, long);
 void launch_knn_topk(const __hip_bfloat16*, const __hip_bfloat16*, unsigned long long*, float*,
                      int*, long, long, int, int, int, hipStream_t);
@@ -1313,6 +1321,130 @@ std::vector<torch::Tensor> knn_topk(torch::Tensor q, torch::Tensor bank, int64_t
   return {val, idx};
 }
 
+// Softmax cross-entropy of logits [B, G, Cp] (+ bias [G, Cp]) against labels [B]
+// over the first C columns, for G heads at once. Returns (loss_sum [G] fp32,
+// correct [G] int64) and, with write_grad, dbias [G, Cp] fp32 after the row
+// gradients (softmax - onehot) * grad_scale have replaced the logits in place.
+// label -1 marks an ignored row. row_blocks: blocks per head, 0 = chosen.
+std::vector<torch::Tensor> probe_ce(torch::Tensor logits, c10::optional<torch::Tensor> bias,
+                                    torch::Tensor labels, int64_t C, double grad_scale,
+                                    bool write_grad, int64_t row_blocks) {
+  CHECK_INPUT(logits);
+  CHECK_INPUT(labels);
+  TORCH_CHECK(logits.dim() == 3, "probe_ce: logits must be [B, G, Cp]");
+  TORCH_CHECK(logits.scalar_type() == at::ScalarType::BFloat16 ||
+                  logits.scalar_type() == at::ScalarType::Float,
+              "probe_ce: logits must be bf16 or fp32");
+  TORCH_CHECK(labels.scalar_type() == at::ScalarType::Long && labels.dim() == 1 &&
+                  labels.size(0) == logits.size(0),
+              "probe_ce: labels must be int64 [B]");
+  TORCH_CHECK(labels.device() == logits.device(), "probe_ce: labels and logits must be on one device");
+  const long B = logits.size(0);
+  const long G = logits.size(1);
+  const long Cp = logits.size(2);
+  TORCH_CHECK(Cp > 0 && Cp % 8 == 0 && Cp <= 2048,
+              "probe_ce: Cp must be a positive multiple of 8 and at most 2048, got ", Cp);
+  TORCH_CHECK(C >= 1 && C <= Cp, "probe_ce: need 1 <= C <= Cp, got C = ", C, ", Cp = ", Cp);
+  TORCH_CHECK(G >= 1 && G <= 65535, "probe_ce: G must be in [1, 65535], got ", G);
+  TORCH_CHECK(B < (1L << 24), "probe_ce: B must be below 2^24 (counts travel as fp32)");
+  TORCH_CHECK(row_blocks >= 0, "probe_ce: row_blocks must be >= 0");
+  TORCH_CHECK((uintptr_t)logits.data_ptr() % 16 == 0, "probe_ce: logits must be 16-byte aligned");
+  const float* bias_ptr = nullptr;
+  if (bias.has_value()) {
+    const torch::Tensor& b = *bias;
+    CHECK_INPUT(b);
+    TORCH_CHECK(b.scalar_type() == at::ScalarType::Float && b.dim() == 2 && b.size(0) == G &&
+                    b.size(1) == Cp,
+                "probe_ce: bias must be fp32 [G, Cp]");
+    TORCH_CHECK(b.device() == logits.device(), "probe_ce: bias and logits must be on one device");
+    TORCH_CHECK((uintptr_t)b.data_ptr() % 16 == 0, "probe_ce: bias must be 16-byte aligned");
+    bias_ptr = b.data_ptr<float>();
+  }
+  int ws_cols, tail;
+  probe_ce_layout((int)G, (int)Cp, write_grad, &ws_cols, &tail);
+  auto fopts = logits.options().dtype(torch::kFloat);
+  if (B == 0) {
+    std::vector<torch::Tensor> ret = {torch::zeros({G}, fopts),
+                                      torch::zeros({G}, fopts.dtype(torch::kLong))};
+    if (write_grad) ret.push_back(torch::zeros({G, Cp}, fopts));
+    return ret;
+  }
+  const int nblk = probe_ce_row_blocks(B, (int)G, (int)std::min<int64_t>(row_blocks, INT_MAX));
+  auto ws = torch::empty({(long)nblk, (long)ws_cols}, fopts);
+  auto out = torch::empty({(long)ws_cols}, fopts);
+  if (logits.scalar_type() == at::ScalarType::Float)
+    launch_probe_ce<float>(logits.data_ptr<float>(), bias_ptr, labels.data_ptr<long>(),
+                           ws.data_ptr<float>(), out.data_ptr<float>(), B, (int)G, (int)Cp, (int)C,
+                           (float)grad_scale, write_grad, nblk, current_stream());
+  else
+    launch_probe_ce<__hip_bfloat16>((__hip_bfloat16*)logits.data_ptr(), bias_ptr,
+                                    labels.data_ptr<long>(), ws.data_ptr<float>(),
+                                    out.data_ptr<float>(), B, (int)G, (int)Cp, (int)C,
+                                    (float)grad_scale, write_grad, nblk, current_stream());
+  std::vector<torch::Tensor> ret = {out.narrow(0, tail, G),
+                                    out.narrow(0, tail + G, G).to(torch::kLong)};
+  if (write_grad) ret.push_back(out.narrow(0, 0, G * Cp).view({G, Cp}));
+  return ret;
+}
+
+// In-place SGD with momentum on w, mom [G, R] fp32 from grad [G, R] (bf16 | fp32):
+// g' = grad + wd[g] w; mom = momentum mom + g'; w -= lr[g] lr_scale mom; with
+// w_lp [G, R] bf16 also w_lp = bf16(w).
+void probe_sgd_(torch::Tensor w, torch::Tensor mom, torch::Tensor grad, torch::Tensor lr,
+                c10::optional<torch::Tensor> wd, double lr_scale, double momentum,
+                c10::optional<torch::Tensor> w_lp) {
+  CHECK_INPUT(w);
+  CHECK_INPUT(mom);
+  CHECK_INPUT(grad);
+  CHECK_INPUT(lr);
+  TORCH_CHECK(w.dim() == 2 && w.scalar_type() == at::ScalarType::Float, "probe_sgd_: w must be fp32 [G, R]");
+  TORCH_CHECK(mom.scalar_type() == at::ScalarType::Float && mom.sizes() == w.sizes(),
+              "probe_sgd_: mom must be fp32 and shaped like w");
+  TORCH_CHECK((grad.scalar_type() == at::ScalarType::Float ||
+               grad.scalar_type() == at::ScalarType::BFloat16) && grad.sizes() == w.sizes(),
+              "probe_sgd_: grad must be bf16 or fp32 and shaped like w");
+  const long G = w.size(0);
+  const long R = w.size(1);
+  TORCH_CHECK(R % 8 == 0, "probe_sgd_: R must be a multiple of 8, got ", R);
+  TORCH_CHECK(G <= 65535, "probe_sgd_: G must be at most 65535, got ", G);
+  TORCH_CHECK(lr.scalar_type() == at::ScalarType::Float && lr.dim() == 1 && lr.size(0) == G,
+              "probe_sgd_: lr must be fp32 [G]");
+  TORCH_CHECK(mom.device() == w.device() && grad.device() == w.device() && lr.device() == w.device(),
+              "probe_sgd_: all tensors must be on one device");
+  TORCH_CHECK((uintptr_t)w.data_ptr() % 16 == 0 && (uintptr_t)mom.data_ptr() % 16 == 0 &&
+                  (uintptr_t)grad.data_ptr() % 16 == 0,
+              "probe_sgd_: w, mom and grad must be 16-byte aligned");
+  const float* wd_ptr = nullptr;
+  if (wd.has_value()) {
+    const torch::Tensor& d = *wd;
+    CHECK_INPUT(d);
+    TORCH_CHECK(d.scalar_type() == at::ScalarType::Float && d.dim() == 1 && d.size(0) == G &&
+                    d.device() == w.device(),
+                "probe_sgd_: wd must be fp32 [G] on w's device");
+    wd_ptr = d.data_ptr<float>();
+  }
+  __hip_bfloat16* lp_ptr = nullptr;
+  if (w_lp.has_value()) {
+    const torch::Tensor& l = *w_lp;
+    CHECK_INPUT(l);
+    TORCH_CHECK(l.scalar_type() == at::ScalarType::BFloat16 && l.sizes() == w.sizes() &&
+                    l.device() == w.device(),
+                "probe_sgd_: w_lp must be bf16, shaped like w, on w's device");
+    TORCH_CHECK((uintptr_t)l.data_ptr() % 16 == 0, "probe_sgd_: w_lp must be 16-byte aligned");
+    lp_ptr = (__hip_bfloat16*)l.data_ptr();
+  }
+  if (G == 0 || R == 0) return;
+  if (grad.scalar_type() == at::ScalarType::Float)
+    launch_probe_sgd<float>(w.data_ptr<float>(), mom.data_ptr<float>(), grad.data_ptr<float>(),
+                            lr.data_ptr<float>(), wd_ptr, lp_ptr, (int)G, R, (float)lr_scale,
+                            (float)momentum, current_stream());
+  else
+    launch_probe_sgd<__hip_bfloat16>(w.data_ptr<float>(), mom.data_ptr<float>(),
+                                     (const __hip_bfloat16*)grad.data_ptr(), lr.data_ptr<float>(),
+                                     wd_ptr, lp_ptr, (int)G, R, (float)lr_scale, (float)momentum,
+                                     current_stream());
+}
+
 }  // namespace
 
 // hipBLASLt fused-epilogue entry points (blaslt_ext.hip)
@@ -1376,6 +1508,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("sinkhorn_div_row", &sinkhorn_div_row);
   mod.def("knn_topk", &knn_topk, py::arg("q"), py::arg("bank"), py::arg("k"),
           py::arg("splits") = 0);
+  mod.def("probe_ce", &probe_ce, py::arg("logits"), py::arg("bias"), py::arg("labels"),
+          py::arg("C"), py::arg("grad_scale"), py::arg("write_grad"), py::arg("row_blocks") = 0);
+  mod.def("probe_sgd_", &probe_sgd_, py::arg("w"), py::arg("mom"), py::arg("grad"), py::arg("lr"),
+          py::arg("wd"), py::arg("lr_scale"), py::arg("momentum"), py::arg("w_lp"));
   mod.def("fmha_fwd", &fmha_fwd);
   mod.def("fmha_rope_fwd", [](torch::Tensor qkv, torch::Tensor sin_t, torch::Tensor cos_t,
                               int64_t prefix) {

@@ -484,8 +484,10 @@ def do_test(cfg, model, iteration: int):
     # DINOV3_EVAL_ON_DEVICE=1: features stay on the device and the k-NN number
     # comes from evaluate_knn_sharded, which is correct for any world size (the
     # sampler gives every rank 1/world of both sets; the default path scores a
-    # rank's val slice against its own train slice only). The linear probe is
-    # the same either way: with world > 1 it still trains on the local shard.
+    # rank's val slice against its own train slice only). The linear number then
+    # is the best head of evaluate_linear_sharded's lr grid, trained on the whole
+    # train set whatever the world size; the default path trains one head on the
+    # local shard.
     on_device = os.environ.get("DINOV3_EVAL_ON_DEVICE", "0") == "1"
     train_feats, train_labels = extract_features(
         backbone, make_data_loader(dataset=train_ds, **kwargs), to_cpu=not on_device)
@@ -493,17 +495,20 @@ def do_test(cfg, model, iteration: int):
         backbone, make_data_loader(dataset=val_ds, **kwargs), to_cpu=not on_device)
     results = {"iteration": iteration}
     if on_device:
-        from ..eval import evaluate_knn_sharded
+        from ..eval import evaluate_knn_sharded, evaluate_linear_sharded
 
         accs = evaluate_knn_sharded(train_feats, train_labels, val_feats, val_labels,
                                     ks=(10, 20, 100, 200))
         results["knn_top1"] = accs[20]
         results.update({f"knn_top1_k{k}": acc for k, acc in accs.items()})
-        train_feats, train_labels = train_feats.cpu(), train_labels.cpu()
-        val_feats, val_labels = val_feats.cpu(), val_labels.cpu()
+        probe = evaluate_linear_sharded(train_feats, train_labels, val_feats, val_labels)
+        results["linear_top1"] = probe["best_top1"]
+        results["linear_best_lr"] = probe["heads"][probe["best_head"]][0]
+        results.update({f"linear_top1_head{i}": acc for i, acc in enumerate(probe["top1"])})
     else:
         results["knn_top1"] = evaluate_knn(train_feats, train_labels, val_feats, val_labels)
-    results["linear_top1"] = evaluate_linear_probe(train_feats, train_labels, val_feats, val_labels)
+        results["linear_top1"] = evaluate_linear_probe(train_feats, train_labels, val_feats,
+                                                       val_labels)
     logger.info("eval results: %s", results)
     return results
 
