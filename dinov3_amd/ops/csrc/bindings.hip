@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "common.h"  // COLRED_MAX_PARTIALS
+#include "fmha_rope.h"  // attention layouts and launchers, launch_probe_mfma
 
 #define CHECK_INPUT(x) \
   TORCH_CHECK(x.is_cuda() && x.is_contiguous(), #x " must be a contiguous HIP tensor")
@@ -105,21 +106,9 @@ void launch_dino_ce_fact_bwd(const __hip_bfloat16*, const __hip_bfloat16*, const
 void launch_sinkhorn_colsum(const float*, float*, int, long, const float*, hipStream_t);
 void launch_sinkhorn_div_row(float*, const float*, int, long, float, const float*, bool,
                              hipStream_t);
-void launch_fmha_rope_fwd(const __hip_bfloat16*, const float*, const float*,
-                          __hip_bfloat16*, float*, int, int, int, int, int, float,
-                          hipStream_t);
-void launch_fmha_rope_bwd_pre(const __hip_bfloat16*, const __hip_bfloat16*, float*, int,
-                              int, int, int, hipStream_t);
-void launch_fmha_rope_bwd_dq(const __hip_bfloat16*, const __hip_bfloat16*, const float*,
-                             const float*, const float*, const float*, __hip_bfloat16*,
-                             int, int, int, int, int, float, hipStream_t);
-void launch_fmha_rope_bwd_dkv(const __hip_bfloat16*, const __hip_bfloat16*, const float*,
-                              const float*, const float*, const float*, __hip_bfloat16*,
-                              int, int, int, int, int, float, hipStream_t);
 void launch_patch_embed_fwd(const __hip_bfloat16*, const __hip_bfloat16*,
                             const __hip_bfloat16*, __hip_bfloat16*, int, int, int, int,
                             int, int, hipStream_t);
-void launch_probe_mfma(const __hip_bfloat16*, const __hip_bfloat16*, float*, hipStream_t);
 void launch_fp8_quant_rows(const __hip_bfloat16*, unsigned char*, float*, long, int, int,
                            hipStream_t);
 int fp8_cols_partials(long, int);
@@ -141,17 +130,6 @@ void launch_probe_sgd(float*, float*, const GT*, const float*, const float*, __h
 int knn_topk_auto_splits(long, long);
 void launch_knn_topk(const __hip_bfloat16*, const __hip_bfloat16*, unsigned long long*, float*,
                      int*, long, long, int, int, int, hipStream_t);
-void launch_fmha_fwd(const __hip_bfloat16*, const __hip_bfloat16*, const __hip_bfloat16*,
-                     __hip_bfloat16*, float*, int, int, int, float, hipStream_t);
-void launch_fmha_bwd_pre(const __hip_bfloat16*, const __hip_bfloat16*, float*, long, int,
-                         hipStream_t);
-void launch_fmha_bwd_dq(const __hip_bfloat16*, const __hip_bfloat16*, const __hip_bfloat16*,
-                        const __hip_bfloat16*, const float*, const float*, __hip_bfloat16*,
-                        int, int, int, float, hipStream_t);
-void launch_fmha_bwd_dkv(const __hip_bfloat16*, const __hip_bfloat16*,
-                         const __hip_bfloat16*, const __hip_bfloat16*, const float*,
-                         const float*, __hip_bfloat16*, __hip_bfloat16*, int, int, int,
-                         float, hipStream_t);
 template <typename T>
 void launch_multi_tensor_ema(T* const*, const T* const*, const long*, const int*,
                              const long*, int, float, hipStream_t);
@@ -799,46 +777,107 @@ torch::Tensor probe_mfma(torch::Tensor A, torch::Tensor B) {
   return C;
 }
 
-std::vector<torch::Tensor> fmha_fwd(torch::Tensor q, torch::Tensor k, torch::Tensor v) {
-  CHECK_INPUT(q);
-  CHECK_INPUT(k);
-  CHECK_INPUT(v);
-  TORCH_CHECK(q.scalar_type() == at::ScalarType::BFloat16, "fmha: bf16 only");
+// Argument checks of the attention wrappers (fmha_*, fmha_rope_*): every tensor
+// the kernels dereference is on the device, contiguous, of the expected dtype
+// and holds as many elements as its shape implies.
+struct AttnDims {
+  int B, H, N, HD;
+  int64_t numel() const { return (int64_t)B * H * N * HD; }  // of q, k, v, o, dO each
+  float scale() const { return 1.0f / std::sqrt((float)HD); }
+};
+
+static void check_attn(const torch::Tensor& x, at::ScalarType dtype, int64_t numel,
+                       const char* name) {
+  TORCH_CHECK(x.defined() && x.is_cuda() && x.is_contiguous(), "fmha: ", name,
+              " must be a contiguous HIP tensor");
+  TORCH_CHECK(x.scalar_type() == dtype, "fmha: ", name, " must be ", dtype, ", got ",
+              x.scalar_type());
+  TORCH_CHECK(x.numel() == numel, "fmha: ", name, " must hold ", numel, " elements, got ",
+              x.numel());
+}
+
+static const __hip_bfloat16* bf16_in(const torch::Tensor& x) {
+  return (const __hip_bfloat16*)x.data_ptr();
+}
+static __hip_bfloat16* bf16_out(torch::Tensor& x) { return (__hip_bfloat16*)x.data_ptr(); }
+
+static AttnDims plain_dims(const torch::Tensor& q, const torch::Tensor& k,
+                           const torch::Tensor& v) {
   TORCH_CHECK(q.dim() == 4, "fmha expects [B, H, N, hd]");
-  const int B = q.size(0), H = q.size(1), N = q.size(2), HD = q.size(3);
-  TORCH_CHECK(HD == 64 || HD == 128, "fmha: head_dim must be 64 or 128, got ", HD);
+  const AttnDims d{(int)q.size(0), (int)q.size(1), (int)q.size(2), (int)q.size(3)};
+  TORCH_CHECK(d.HD == 64 || d.HD == 128, "fmha: head_dim must be 64 or 128, got ", d.HD);
+  TORCH_CHECK(k.sizes() == q.sizes() && v.sizes() == q.sizes(), "fmha: q, k, v differ in shape");
+  check_attn(q, at::kBFloat16, d.numel(), "q");
+  check_attn(k, at::kBFloat16, d.numel(), "k");
+  check_attn(v, at::kBFloat16, d.numel(), "v");
+  return d;
+}
+
+static AttnDims packed_dims(const torch::Tensor& qkv) {
+  TORCH_CHECK(qkv.dim() == 5 && qkv.size(2) == 3, "qkv must be [B, N, 3, H, hd]");
+  const AttnDims d{(int)qkv.size(0), (int)qkv.size(3), (int)qkv.size(1), (int)qkv.size(4)};
+  TORCH_CHECK(d.HD == 64 || d.HD == 128, "head_dim must be 64 or 128");
+  check_attn(qkv, at::kBFloat16, 3 * d.numel(), "qkv");
+  return d;
+}
+
+// o, lse (forward results) and dout, as the backward wrappers receive them
+static void check_bwd_inputs(const AttnDims& d, const torch::Tensor& dout,
+                             const torch::Tensor& o, const torch::Tensor& lse) {
+  check_attn(dout, at::kBFloat16, d.numel(), "dout");
+  check_attn(o, at::kBFloat16, d.numel(), "o");
+  check_attn(lse, at::kFloat, (int64_t)d.B * d.H * d.N, "lse");
+}
+
+// fp32 [N - prefix, hd] sin / cos tables, or both empty for no RoPE
+struct RopeTables {
+  const float *sin, *cos;
+  int P;
+};
+
+static RopeTables rope_tables(const AttnDims& d, const torch::Tensor& sin_t,
+                              const torch::Tensor& cos_t, int64_t prefix) {
+  const int P = d.N - (int)prefix;
+  if (!(sin_t.defined() && sin_t.numel() > 0)) return {nullptr, nullptr, P};
+  TORCH_CHECK(sin_t.dim() == 2 && sin_t.size(0) == P, "rope table rows must equal N - prefix");
+  TORCH_CHECK(sin_t.size(1) == d.HD, "rope tables must be [N - prefix, hd]");
+  check_attn(sin_t, at::kFloat, (int64_t)P * d.HD, "sin_t");
+  TORCH_CHECK(cos_t.defined() && cos_t.sizes() == sin_t.sizes(), "cos_t must match sin_t in shape");
+  check_attn(cos_t, at::kFloat, (int64_t)P * d.HD, "cos_t");
+  return {sin_t.data_ptr<float>(), cos_t.data_ptr<float>(), P};
+}
+
+std::vector<torch::Tensor> fmha_fwd(torch::Tensor q, torch::Tensor k, torch::Tensor v) {
+  using L = fmha_rope::PlainLayout;
+  const AttnDims d = plain_dims(q, k, v);
   auto o = torch::empty_like(q);
-  auto lse = torch::empty({B, H, N}, q.options().dtype(torch::kFloat));
-  const float scale = 1.0f / std::sqrt((float)HD);
-  launch_fmha_fwd((const __hip_bfloat16*)q.data_ptr(), (const __hip_bfloat16*)k.data_ptr(),
-                  (const __hip_bfloat16*)v.data_ptr(), (__hip_bfloat16*)o.data_ptr(),
-                  lse.data_ptr<float>(), B * H, N, HD, scale, current_stream());
+  auto lse = torch::empty({d.B, d.H, d.N}, q.options().dtype(torch::kFloat));
+  fmha_rope::launch_fwd<L>(L::Qkv{bf16_in(q), bf16_in(k), bf16_in(v)}, nullptr, nullptr,
+                           bf16_out(o), lse.data_ptr<float>(), d.B, d.H, d.N, d.N, d.HD,
+                           d.scale(), current_stream());
   return {o, lse};
 }
 
 std::vector<torch::Tensor> fmha_bwd(torch::Tensor dout, torch::Tensor q, torch::Tensor k,
                                     torch::Tensor v, torch::Tensor o, torch::Tensor lse) {
-  CHECK_INPUT(dout);
-  const int B = q.size(0), H = q.size(1), N = q.size(2), HD = q.size(3);
-  const float scale = 1.0f / std::sqrt((float)HD);
-  auto D = torch::empty({B, H, N}, q.options().dtype(torch::kFloat));
+  using L = fmha_rope::PlainLayout;
+  const AttnDims d = plain_dims(q, k, v);
+  check_bwd_inputs(d, dout, o, lse);
+  auto D = torch::empty({d.B, d.H, d.N}, q.options().dtype(torch::kFloat));
   auto dq = torch::empty_like(q);
   auto dk = torch::empty_like(k);
   auto dv = torch::empty_like(v);
+  const L::Qkv in{bf16_in(q), bf16_in(k), bf16_in(v)};
+  const L::DQkv grad{bf16_out(dq), bf16_out(dk), bf16_out(dv)};
   auto stream = current_stream();
-  launch_fmha_bwd_pre((const __hip_bfloat16*)dout.data_ptr(),
-                      (const __hip_bfloat16*)o.data_ptr(), D.data_ptr<float>(),
-                      (long)B * H * N, HD, stream);
-  launch_fmha_bwd_dq((const __hip_bfloat16*)q.data_ptr(), (const __hip_bfloat16*)k.data_ptr(),
-                     (const __hip_bfloat16*)v.data_ptr(),
-                     (const __hip_bfloat16*)dout.data_ptr(), lse.data_ptr<float>(),
-                     D.data_ptr<float>(), (__hip_bfloat16*)dq.data_ptr(), B * H, N, HD,
-                     scale, stream);
-  launch_fmha_bwd_dkv((const __hip_bfloat16*)q.data_ptr(), (const __hip_bfloat16*)k.data_ptr(),
-                      (const __hip_bfloat16*)v.data_ptr(),
-                      (const __hip_bfloat16*)dout.data_ptr(), lse.data_ptr<float>(),
-                      D.data_ptr<float>(), (__hip_bfloat16*)dk.data_ptr(),
-                      (__hip_bfloat16*)dv.data_ptr(), B * H, N, HD, scale, stream);
+  fmha_rope::launch_bwd_pre<L>(bf16_in(dout), bf16_in(o), D.data_ptr<float>(), d.B, d.H, d.N,
+                               d.HD, stream);
+  fmha_rope::launch_bwd_dq<L>(in, bf16_in(dout), nullptr, nullptr, lse.data_ptr<float>(),
+                              D.data_ptr<float>(), grad, d.B, d.H, d.N, d.N, d.HD, d.scale(),
+                              stream);
+  fmha_rope::launch_bwd_dkv<L>(in, bf16_in(dout), nullptr, nullptr, lse.data_ptr<float>(),
+                               D.data_ptr<float>(), grad, d.B, d.H, d.N, d.N, d.HD, d.scale(),
+                               stream);
   return {dq, dk, dv};
 }
 
@@ -868,27 +907,17 @@ torch::Tensor patch_embed_fwd(torch::Tensor x, torch::Tensor w, torch::Tensor bi
 std::vector<torch::Tensor> fmha_rope_fwd_out(torch::Tensor qkv, torch::Tensor sin_t,
                                              torch::Tensor cos_t, int64_t prefix,
                                              torch::Tensor out_o) {
-  CHECK_INPUT(qkv);
-  TORCH_CHECK(qkv.dim() == 5 && qkv.size(2) == 3, "qkv must be [B, N, 3, H, hd]");
-  TORCH_CHECK(qkv.scalar_type() == at::ScalarType::BFloat16);
-  const int B = qkv.size(0), N = qkv.size(1), H = qkv.size(3), HD = qkv.size(4);
-  TORCH_CHECK(HD == 64 || HD == 128, "head_dim must be 64 or 128");
-  const bool has_rope = sin_t.defined() && sin_t.numel() > 0;
-  const int P = has_rope ? (int)sin_t.size(0) : N - (int)prefix;
-  if (has_rope) {
-    TORCH_CHECK(sin_t.scalar_type() == at::ScalarType::Float && sin_t.is_contiguous());
-    TORCH_CHECK(P == N - prefix, "rope table rows must equal N - prefix");
-  }
-  torch::Tensor o = out_o.defined() && out_o.numel() > 0 ? out_o
-                                                        : torch::empty({B, N, H, HD}, qkv.options());
-  TORCH_CHECK(o.is_contiguous() && o.numel() == (long)B * N * H * HD);
-  auto lse = torch::empty({B, H, N}, qkv.options().dtype(torch::kFloat));
-  const float scale = 1.0f / std::sqrt((float)HD);
-  launch_fmha_rope_fwd((const __hip_bfloat16*)qkv.data_ptr(),
-                       has_rope ? sin_t.data_ptr<float>() : nullptr,
-                       has_rope ? cos_t.data_ptr<float>() : nullptr,
-                       (__hip_bfloat16*)o.data_ptr(), lse.data_ptr<float>(), B, H, N, P,
-                       HD, scale, current_stream());
+  using L = fmha_rope::PackedLayout;
+  const AttnDims d = packed_dims(qkv);
+  const RopeTables rope = rope_tables(d, sin_t, cos_t, prefix);
+  torch::Tensor o = out_o.defined() && out_o.numel() > 0
+                        ? out_o
+                        : torch::empty({d.B, d.N, d.H, d.HD}, qkv.options());
+  check_attn(o, at::kBFloat16, d.numel(), "out_o");
+  auto lse = torch::empty({d.B, d.H, d.N}, qkv.options().dtype(torch::kFloat));
+  fmha_rope::launch_fwd<L>(L::Qkv{bf16_in(qkv)}, rope.sin, rope.cos, bf16_out(o),
+                           lse.data_ptr<float>(), d.B, d.H, d.N, rope.P, d.HD, d.scale(),
+                           current_stream());
   return {o, lse};
 }
 
@@ -896,31 +925,25 @@ torch::Tensor fmha_rope_bwd_out(torch::Tensor dout, torch::Tensor qkv, torch::Te
                                 torch::Tensor lse, torch::Tensor sin_t,
                                 torch::Tensor cos_t, int64_t prefix,
                                 torch::Tensor out_dqkv) {
-  CHECK_INPUT(dout);
-  const int B = qkv.size(0), N = qkv.size(1), H = qkv.size(3), HD = qkv.size(4);
-  const bool has_rope = sin_t.defined() && sin_t.numel() > 0;
-  const int P = N - (int)prefix;
-  const float scale = 1.0f / std::sqrt((float)HD);
-  auto D = torch::empty({B, H, N}, qkv.options().dtype(torch::kFloat));
+  using L = fmha_rope::PackedLayout;
+  const AttnDims d = packed_dims(qkv);
+  check_bwd_inputs(d, dout, o, lse);
+  const RopeTables rope = rope_tables(d, sin_t, cos_t, prefix);
+  auto D = torch::empty({d.B, d.H, d.N}, qkv.options().dtype(torch::kFloat));
   torch::Tensor dqkv = out_dqkv.defined() && out_dqkv.numel() > 0 ? out_dqkv
                                                                   : torch::empty_like(qkv);
+  check_attn(dqkv, at::kBFloat16, 3 * d.numel(), "out_dqkv");
+  const L::Qkv in{bf16_in(qkv)};
+  const L::DQkv grad{bf16_out(dqkv)};
   auto stream = current_stream();
-  launch_fmha_rope_bwd_pre((const __hip_bfloat16*)dout.data_ptr(),
-                           (const __hip_bfloat16*)o.data_ptr(), D.data_ptr<float>(), B, H,
-                           N, HD, stream);
-  launch_fmha_rope_bwd_dq((const __hip_bfloat16*)qkv.data_ptr(),
-                          (const __hip_bfloat16*)dout.data_ptr(),
-                          has_rope ? sin_t.data_ptr<float>() : nullptr,
-                          has_rope ? cos_t.data_ptr<float>() : nullptr,
-                          lse.data_ptr<float>(), D.data_ptr<float>(),
-                          (__hip_bfloat16*)dqkv.data_ptr(), B, H, N, P, HD, scale, stream);
-  launch_fmha_rope_bwd_dkv((const __hip_bfloat16*)qkv.data_ptr(),
-                           (const __hip_bfloat16*)dout.data_ptr(),
-                           has_rope ? sin_t.data_ptr<float>() : nullptr,
-                           has_rope ? cos_t.data_ptr<float>() : nullptr,
-                           lse.data_ptr<float>(), D.data_ptr<float>(),
-                           (__hip_bfloat16*)dqkv.data_ptr(), B, H, N, P, HD, scale,
-                           stream);
+  fmha_rope::launch_bwd_pre<L>(bf16_in(dout), bf16_in(o), D.data_ptr<float>(), d.B, d.H, d.N,
+                               d.HD, stream);
+  fmha_rope::launch_bwd_dq<L>(in, bf16_in(dout), rope.sin, rope.cos, lse.data_ptr<float>(),
+                              D.data_ptr<float>(), grad, d.B, d.H, d.N, rope.P, d.HD,
+                              d.scale(), stream);
+  fmha_rope::launch_bwd_dkv<L>(in, bf16_in(dout), rope.sin, rope.cos, lse.data_ptr<float>(),
+                               D.data_ptr<float>(), grad, d.B, d.H, d.N, rope.P, d.HD,
+                               d.scale(), stream);
   return dqkv;
 }
 

@@ -1,60 +1,33 @@
-// Fused RoPE + multi-head attention on the raw QKV projection (K5 + K6).
+// Fused RoPE + multi-head attention, forward and FA2-style backward (K5 + K6).
 //
-// Reads qkv [B, N, 3, H, hd] bf16 (the qkv GEMM output, no permutes), applies
-// rotate-half RoPE (fp32 sin/cos [P, hd] tables, prefix tokens pass through)
-// to Q in-register and to K at LDS staging, writes O token-major [B, N, H, hd]
-// so the out-projection GEMM consumes it directly. Backward writes dq/dk/dv
-// into ONE dqkv buffer of the same layout and applies the inverse rotation to
-// dQ/dK in the accumulator epilogues.
+// One kernel of each kind (fwd, dq, dkv, rowsum preprocess), parameterised at
+// compile time by a memory-layout policy (fmha_rope.h):
+// - PackedLayout reads qkv [B, N, 3, H, hd] bf16 (the qkv GEMM output, no
+//   permutes) and writes O token-major [B, N, H, hd] so the out-projection
+//   GEMM consumes it directly; backward fills ONE dqkv buffer of qkv's layout.
+// - PlainLayout serves the q/k/v [B, H, N, hd] entry points (ops.fmha).
+// Rotate-half RoPE (fp32 sin/cos [P, hd] tables, prefix tokens pass through)
+// is applied to Q in-register and to K at LDS staging; the inverse rotation of
+// dQ/dK runs in the accumulator epilogues. sin_t == nullptr: no RoPE.
 //
-// Same MFMA machinery as fmha.hip (swapped S^T, permlane32_swap repack);
-// see that file for the fragment-layout contract (probe-verified).
+// Design (MI355X / CDNA4):
+// - v_mfma_f32_32x32x16_bf16 tiles (fragment layouts: mfma.h); wave64; each
+//   wave owns 32 q rows (fwd, dq) or 32 k rows (dkv) of a (batch, head).
+// - Scores are computed SWAPPED — S^T = K @ Q^T — so each lane holds a full q
+//   column and the online-softmax row reduction is 16 lane-local values + one
+//   shfl_xor(32). P^T (fp32 accum) repacks into the next MFMA's bf16 fragment
+//   with v_cvt_pk_bf16_f32 pairs + v_permlane32_swap (pack_fragment).
+// - K/V tiles of 2*KVB keys are staged in LDS per barrier pair (V or K also
+//   transposed so the second MFMA's A-fragment reads contiguously); the next
+//   tile's global loads are issued before the compute phase.
+// - backward recomputes P from the saved logsumexp. Three kernels: preprocess
+//   D = rowsum(dO*O); dQ (loop over k tiles); dK/dV (loop over q tiles).
 
-#include "common.h"
+#include "fmha_rope.h"
+#include "mfma.h"
 #include <cstdlib>
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-
-#define MFMA32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0)
-
 namespace fmha_rope {
-
-DEV_INLINE unsigned cvt_pk_bf16(float lo, float hi) {
-  unsigned r;
-  asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-  return r;
-}
-
-DEV_INLINE void permlane32_swap(unsigned& a, unsigned& b) {
-  auto r = __builtin_amdgcn_permlane32_swap(a, b, false, false);
-  a = r[0];
-  b = r[1];
-}
-
-DEV_INLINE bf16x8 pack_fragment(const float* s, int base) {
-  unsigned r01 = cvt_pk_bf16(s[base + 0], s[base + 1]);
-  unsigned r23 = cvt_pk_bf16(s[base + 2], s[base + 3]);
-  unsigned r45 = cvt_pk_bf16(s[base + 4], s[base + 5]);
-  unsigned r67 = cvt_pk_bf16(s[base + 6], s[base + 7]);
-  permlane32_swap(r01, r45);
-  permlane32_swap(r23, r67);
-  union {
-    unsigned u[4];
-    bf16x8 v;
-  } out;
-  out.u[0] = r01;
-  out.u[1] = r23;
-  out.u[2] = r45;
-  out.u[3] = r67;
-  return out.v;
-}
-
-DEV_INLINE bf16x8 load8(const __hip_bfloat16* p) {
-  return *reinterpret_cast<const bf16x8*>(p);
-}
-
-DEV_INLINE int c_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
 DEV_INLINE float b2f(__bf16 x) {
   union { float f; unsigned i; } v;
@@ -86,16 +59,211 @@ DEV_INLINE void rope_rotate8(bf16x8& lo, bf16x8& hi, const float* sinrow,
   hi = hi_out.v;
 }
 
-// qkv addressing: element (n, which, d) for fixed (b, h)
-// offset = ((((long)b*N + n)*3 + which)*H + h)*hd + d
-struct QkvView {
-  const __hip_bfloat16* base;  // qkv + (b, h) folded: base = qkv + (b*N*3*H + h)*hd
-  long row_stride;             // 3*H*hd
-  long which_stride;           // H*hd
-  DEV_INLINE const __hip_bfloat16* at(int n, int which, int d) const {
-    return base + (long)n * row_stride + which * which_stride + d;
+// ---------------------------------------------------------------------------
+// pieces shared by the kernels
+// ---------------------------------------------------------------------------
+
+// blockIdx.x = b*H + h; a wave's lanes split into two halves of 32
+struct BlockCtx {
+  int b, h, wave, lane, hhalf, l31;
+  int prefix;     // rows [0, prefix) are not rotated
+  long stat_off;  // (b*H + h)*N: this head's row 0 of lse / D
+  bool use_rope;
+};
+
+DEV_INLINE BlockCtx block_ctx(int H, int N, int P, const float* sin_t) {
+  BlockCtx c;
+  c.b = blockIdx.x / H;
+  c.h = blockIdx.x % H;
+  c.wave = threadIdx.x / 64;
+  c.lane = threadIdx.x & 63;
+  c.hhalf = c.lane >> 5;
+  c.l31 = c.lane & 31;
+  c.prefix = N - P;
+  c.stat_off = ((long)c.b * H + c.h) * N;
+  c.use_rope = (sin_t != nullptr);
+  return c;
+}
+
+// rotate the KSLICES A/B fragments of row n (slice s pairs with s + KSLICES/2)
+template <int KSLICES>
+DEV_INLINE void rope_fragments(bf16x8 (&f)[KSLICES], const float* sin_t, const float* cos_t,
+                               int n, const BlockCtx& c) {
+  constexpr int HD = KSLICES * 16;
+  const int p = n - c.prefix;
+  if (c.use_rope && p >= 0) {
+    const float* srow = sin_t + (long)p * HD;
+    const float* crow = cos_t + (long)p * HD;
+#pragma unroll
+    for (int s2 = 0; s2 < KSLICES / 2; ++s2)
+      rope_rotate8(f[s2], f[s2 + KSLICES / 2], srow, crow, s2 * 16 + c.hhalf * 8);
+  }
+}
+
+// acc_row += a0 @ b0 + a1 @ b1 (one 32x32 C tile, k = 32)
+DEV_INLINE void mfma2_acc(float (&acc_row)[16], bf16x8 a0, bf16x8 b0, bf16x8 a1, bf16x8 b1) {
+  f32x16 acc;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc[r] = acc_row[r];
+  acc = MFMA32(a0, b0, acc);
+  acc = MFMA32(a1, b1, acc);
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc_row[r] = acc[r];
+}
+
+// inverse rope on a gradient accumulator of row n (C rows = d): pairs
+// (d, d + hd/2) = (tile t, tile t + DTILES/2) reg r
+template <int DTILES>
+DEV_INLINE void rope_inverse(float (&acc)[DTILES][16], const float* sin_t, const float* cos_t,
+                             int n, const BlockCtx& c) {
+  const int p = n - c.prefix;
+  if (c.use_rope && p >= 0) {
+    const float* srow = sin_t + (long)p * DTILES * 32;
+    const float* crow = cos_t + (long)p * DTILES * 32;
+#pragma unroll
+    for (int t = 0; t < DTILES / 2; ++t)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int d = t * 32 + c_row(r, c.hhalf);
+        const float co = crow[d], s = srow[d];
+        const float glo = acc[t][r], ghi = acc[t + DTILES / 2][r];
+        acc[t][r] = glo * co + ghi * s;
+        acc[t + DTILES / 2][r] = ghi * co - glo * s;
+      }
+  }
+}
+
+// accumulators are C[d rows, this lane's row as column]: transposed bf16 store
+// of acc * mul (the forward's 1/l; the default folds away)
+template <int DTILES>
+DEV_INLINE void store_rows_bf16(__hip_bfloat16* row, const float (&acc)[DTILES][16], int hhalf,
+                                float mul = 1.0f) {
+#pragma unroll
+  for (int t = 0; t < DTILES; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int d = t * 32 + c_row(r, hhalf);
+      *reinterpret_cast<short*>(row + d) = f32_to_bf16(acc[t][r] * mul);
+    }
+}
+
+// 8 bf16 at p, p + stride, ... as one fragment
+DEV_INLINE bf16x8 gather8(const __hip_bfloat16* p, int stride) {
+  union { unsigned u[4]; bf16x8 v8; } f;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) reinterpret_cast<__hip_bfloat16*>(&f)[e] = p[e * stride];
+  return f.v8;
+}
+
+// LDS geometry of the K/V tile of fwd and dq: 2*KVB keys per barrier pair,
+// row-major [ROWS][LDS_STRIDE] (k_lds, v_lds) and transposed [HD][T_STRIDE].
+template <int HD, int KVB>
+struct KvTile {
+  static constexpr int ROWS = 2 * KVB;
+  static constexpr int LDS_STRIDE = HD + 8;  // +16 B pad vs bank conflicts
+  static constexpr int T_STRIDE = ROWS + 8;
+  static constexpr int TILE = ROWS * LDS_STRIDE;  // elements of k_lds / v_lds
+  static constexpr int T_TILE = HD * T_STRIDE;    // elements of t_lds
+};
+
+// Staging of that tile. K rows go (rope applied at the write) to k_lds.
+// KT = false (fwd): V goes transposed to t_lds. KT = true (dq): rope'd K also
+// goes transposed to t_lds and V goes row-major to v_lds.
+// T14 async-STAGE split: each thread owns K_IPT K pair-chunks and V_IPT V
+// chunks of the tile in registers; the next tile's global loads are issued
+// BEFORE the compute phase so HBM latency hides under the MFMAs instead of
+// draining at the pre-compute barrier.
+template <class L, int HD, int NT, int KVB, bool KT>
+struct KvStage : KvTile<HD, KVB> {
+  using KvTile<HD, KVB>::ROWS;
+  using KvTile<HD, KVB>::LDS_STRIDE;
+  using KvTile<HD, KVB>::T_STRIDE;
+  static constexpr int HALF = HD / 2;
+  static constexpr int PAIRS_PER_ROW = HALF / 8;  // K pair-items per row
+  static constexpr int PER_ROW = HD / 8;          // V items per row
+  static constexpr int K_ITEMS = ROWS * PAIRS_PER_ROW;
+  static constexpr int V_ITEMS = ROWS * PER_ROW;
+  static constexpr int K_IPT = (K_ITEMS + NT - 1) / NT;
+  static constexpr int V_IPT = (V_ITEMS + NT - 1) / NT;
+
+  bf16x8 klo[K_IPT], khi[K_IPT], vreg[V_IPT];
+
+  DEV_INLINE void issue_loads(const L& lay, const typename L::Qkv& in, int kbase0, int N) {
+#pragma unroll
+    for (int j = 0; j < K_IPT; ++j) {
+      const int item = threadIdx.x + j * NT;
+      const int krow = kbase0 + item / PAIRS_PER_ROW;
+      const int c0 = (item % PAIRS_PER_ROW) * 8;
+      const bool ok = item < K_ITEMS && krow < N;
+      klo[j] = ok ? load8(lay.at(in, krow, 1, c0)) : bf16x8{};
+      khi[j] = ok ? load8(lay.at(in, krow, 1, c0 + HALF)) : bf16x8{};
+    }
+#pragma unroll
+    for (int j = 0; j < V_IPT; ++j) {
+      const int idx = threadIdx.x + j * NT;
+      const int krow = kbase0 + idx / PER_ROW;
+      vreg[j] = (idx < V_ITEMS && krow < N) ? load8(lay.at(in, krow, 2, (idx % PER_ROW) * 8))
+                                            : bf16x8{};
+    }
+  }
+
+  DEV_INLINE void write_tile(int kbase0, int N, const BlockCtx& c, const float* sin_t,
+                             const float* cos_t, __hip_bfloat16* k_lds,
+                             __hip_bfloat16* v_lds, __hip_bfloat16* t_lds) {
+#pragma unroll
+    for (int j = 0; j < K_IPT; ++j) {
+      const int item = threadIdx.x + j * NT;
+      if (item < K_ITEMS) {
+        const int lrow = item / PAIRS_PER_ROW;
+        const int c0 = (item % PAIRS_PER_ROW) * 8;
+        const int krow = kbase0 + lrow;
+        const int p = krow - c.prefix;
+        if (c.use_rope && krow < N && p >= 0)
+          rope_rotate8(klo[j], khi[j], sin_t + (long)p * HD, cos_t + (long)p * HD, c0);
+        *reinterpret_cast<bf16x8*>(&k_lds[lrow * LDS_STRIDE + c0]) = klo[j];
+        *reinterpret_cast<bf16x8*>(&k_lds[lrow * LDS_STRIDE + HALF + c0]) = khi[j];
+        if constexpr (KT) {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            t_lds[(c0 + e) * T_STRIDE + lrow] = reinterpret_cast<__hip_bfloat16*>(&klo[j])[e];
+            t_lds[(c0 + HALF + e) * T_STRIDE + lrow] = reinterpret_cast<__hip_bfloat16*>(&khi[j])[e];
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < V_IPT; ++j) {
+      const int idx = threadIdx.x + j * NT;
+      if (idx < V_ITEMS) {
+        const int row = idx / PER_ROW;
+        const int c8 = (idx % PER_ROW) * 8;
+        if constexpr (KT) {
+          *reinterpret_cast<bf16x8*>(&v_lds[row * LDS_STRIDE + c8]) = vreg[j];
+        } else {
+#pragma unroll
+          for (int e = 0; e < 8; ++e)
+            t_lds[(c8 + e) * T_STRIDE + row] = reinterpret_cast<__hip_bfloat16*>(&vreg[j])[e];
+        }
+      }
+    }
   }
 };
+
+constexpr int SUBK = 32;  // keys per MFMA tile (fixed by the 32x32 MFMA)
+
+// ---------------------------------------------------------------------------
+// MFMA layout probe: C[32,32] = A[32,16] @ B[16,32] with the layouts of mfma.h
+// ---------------------------------------------------------------------------
+__global__ void probe_mfma_kernel(const __hip_bfloat16* __restrict__ A,
+                                  const __hip_bfloat16* __restrict__ B,
+                                  float* __restrict__ C) {
+  const int lane = threadIdx.x & 63;
+  const int h = lane >> 5;
+  const int i = lane & 31;
+  f32x16 c = {};
+  c = MFMA32(gather8(A + i * 16 + h * 8, 1), gather8(B + h * 8 * 32 + i, 32), c);
+  for (int r = 0; r < 16; ++r) C[c_row(r, h) * 32 + i] = c[r];
+}
 
 // ---------------------------------------------------------------------------
 // Forward
@@ -106,61 +274,51 @@ struct QkvView {
 // QLDS parks the rotated Q fragments in LDS in their REGISTER layout (lane-
 // indexed, conflict-free b128), PREFETCH=false drops the register double
 // buffer; together they fit 2 waves/SIMD.
-template <int HD, int NT = 256, bool QLDS = false, bool PREFETCH = true, int MINW = 1,
-          int KVB = 32>
+template <int HD, int NT, bool QLDS, int KVB>
+struct FwdSmem {  // k_lds | vt_lds | per-wave Q fragments (index = slice, lane)
+  using Tile = KvTile<HD, KVB>;
+  static constexpr int Q_WAVE = (HD / 16) * 64 * 8;
+  static constexpr int VT_OFF = Tile::TILE;
+  static constexpr int Q_OFF = VT_OFF + Tile::T_TILE;
+  static constexpr size_t BYTES =
+      (Q_OFF + (QLDS ? (NT / 64) * Q_WAVE : 0)) * sizeof(__hip_bfloat16);
+};
+
+template <class L, int HD, int NT = 256, bool QLDS = false, bool PREFETCH = true,
+          int MINW = 1, int KVB = 32>
 __global__ __launch_bounds__(NT, MINW) void fwd_kernel(
-    const __hip_bfloat16* __restrict__ qkv, const float* __restrict__ sin_t,
-    const float* __restrict__ cos_t, __hip_bfloat16* __restrict__ o,
-    float* __restrict__ lse, int B, int H, int N, int P, float scale) {
+    typename L::Qkv in, const float* __restrict__ sin_t, const float* __restrict__ cos_t,
+    __hip_bfloat16* __restrict__ o, float* __restrict__ lse, int B, int H, int N, int P,
+    float scale) {
+  using Smem = FwdSmem<HD, NT, QLDS, KVB>;
   constexpr int KSLICES = HD / 16;
   constexpr int DTILES = HD / 32;
-  constexpr int LDS_STRIDE = HD + 8;
-  constexpr int VT_STRIDE = 2 * KVB + 8;
-  constexpr int HALF = HD / 2;
+  constexpr int LDS_STRIDE = Smem::Tile::LDS_STRIDE;
+  constexpr int VT_STRIDE = Smem::Tile::T_STRIDE;
 
-  const int bh = blockIdx.x;
-  const int b = bh / H;
-  const int h = bh % H;
-  const int wave = threadIdx.x / 64;
-  const int lane = threadIdx.x & 63;
-  const int hhalf = lane >> 5;
-  const int l31 = lane & 31;
-  const int q0 = blockIdx.y * (NT / 2) + wave * 32;
-  const int prefix = N - P;
-  const bool use_rope = (sin_t != nullptr);
-
-  QkvView qv;
-  qv.base = qkv + ((long)b * N * 3 * H + h) * HD;
-  qv.row_stride = (long)3 * H * HD;
-  qv.which_stride = (long)H * HD;
+  const BlockCtx c = block_ctx(H, N, P, sin_t);
+  const L lay(c.b, c.h, H, N, HD);
+  const int hhalf = c.hhalf, l31 = c.l31;
+  const int q0 = blockIdx.y * (NT / 2) + c.wave * 32;
 
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   __hip_bfloat16* k_lds = reinterpret_cast<__hip_bfloat16*>(smem_raw);
-  __hip_bfloat16* vt_lds = k_lds + 2 * KVB * LDS_STRIDE;
-  // per-wave Q fragment store in register layout: index = slice, lane
-  __hip_bfloat16* q_lds = vt_lds + HD * VT_STRIDE + (QLDS ? wave * KSLICES * 64 * 8 : 0);
+  __hip_bfloat16* vt_lds = k_lds + Smem::VT_OFF;
+  __hip_bfloat16* q_lds = k_lds + Smem::Q_OFF + (QLDS ? c.wave * Smem::Q_WAVE : 0);
 
   // Q fragments (+ rope)
+  const int qrow = q0 + l31;
   bf16x8 qf[QLDS ? 1 : KSLICES];
   {
     bf16x8 qtmp[KSLICES];
-    const int qrow = q0 + l31;
     const int safe = qrow < N ? qrow : (N - 1);
 #pragma unroll
-    for (int s = 0; s < KSLICES; ++s) qtmp[s] = load8(qv.at(safe, 0, s * 16 + hhalf * 8));
-    const int p = safe - prefix;
-    if (use_rope && p >= 0) {
-      const float* srow = sin_t + (long)p * HD;
-      const float* crow = cos_t + (long)p * HD;
-#pragma unroll
-      for (int s2 = 0; s2 < KSLICES / 2; ++s2) {
-        rope_rotate8(qtmp[s2], qtmp[s2 + KSLICES / 2], srow, crow, s2 * 16 + hhalf * 8);
-      }
-    }
+    for (int s = 0; s < KSLICES; ++s) qtmp[s] = load8(lay.at(in, safe, 0, s * 16 + hhalf * 8));
+    rope_fragments(qtmp, sin_t, cos_t, safe, c);
     if constexpr (QLDS) {
 #pragma unroll
       for (int s = 0; s < KSLICES; ++s)
-        *reinterpret_cast<bf16x8*>(&q_lds[(s * 64 + lane) * 8]) = qtmp[s];
+        *reinterpret_cast<bf16x8*>(&q_lds[(s * 64 + c.lane) * 8]) = qtmp[s];
     } else {
 #pragma unroll
       for (int s = 0; s < KSLICES; ++s) qf[s] = qtmp[s];
@@ -174,208 +332,125 @@ __global__ __launch_bounds__(NT, MINW) void fwd_kernel(
     for (int r = 0; r < 16; ++r) o_acc[t][r] = 0.f;
   float m_run = -INFINITY, l_run = 0.f;
 
-  // T14 async-STAGE split: each thread owns ONE K pair-chunk and up to two V
-  // chunks of the staged 64-key tile; the next tile's global loads are issued
-  // BEFORE the compute phase so HBM latency hides under the MFMAs instead of
-  // draining at the pre-compute barrier.
-  constexpr int PAIRS_PER_ROW = HALF / 8;     // K pair-items per row
-  constexpr int PER_ROW = HD / 8;             // V items per row
-  constexpr int K_ITEMS = 2 * KVB * PAIRS_PER_ROW;   // 256 (hd64) / 512 (hd128)
-  constexpr int K_ITEMS_PER_THREAD = (K_ITEMS + NT - 1) / NT;
-  constexpr int V_ITEMS_PER_THREAD = (2 * KVB * PER_ROW + NT - 1) / NT;
-
-  bf16x8 klo[K_ITEMS_PER_THREAD], khi[K_ITEMS_PER_THREAD];
-  bf16x8 vreg[V_ITEMS_PER_THREAD];
-  auto issue_loads = [&](int kbase0) {
-#pragma unroll
-    for (int j = 0; j < K_ITEMS_PER_THREAD; ++j) {
-      const int item = threadIdx.x + j * NT;
-      const int krow = kbase0 + item / PAIRS_PER_ROW;
-      const int c0 = (item % PAIRS_PER_ROW) * 8;
-      const bool ok = item < K_ITEMS && krow < N;
-      klo[j] = ok ? load8(qv.at(krow, 1, c0)) : bf16x8{};
-      khi[j] = ok ? load8(qv.at(krow, 1, c0 + HALF)) : bf16x8{};
-    }
-#pragma unroll
-    for (int j = 0; j < V_ITEMS_PER_THREAD; ++j) {
-      const int idx = threadIdx.x + j * NT;
-      const int row = idx / PER_ROW;
-      const int krow = kbase0 + row;
-      vreg[j] = (idx < 2 * KVB * PER_ROW && krow < N) ? load8(qv.at(krow, 2, (idx % PER_ROW) * 8))
-                                                      : bf16x8{};
-    }
-  };
-  auto write_tile = [&](int kbase0) {
-#pragma unroll
-    for (int j = 0; j < K_ITEMS_PER_THREAD; ++j) {
-      const int item = threadIdx.x + j * NT;
-      if (item < K_ITEMS) {
-        const int lrow = item / PAIRS_PER_ROW;
-        const int c0 = (item % PAIRS_PER_ROW) * 8;
-        const int krow = kbase0 + lrow;
-        const int p = krow - prefix;
-        if (use_rope && krow < N && p >= 0)
-          rope_rotate8(klo[j], khi[j], sin_t + (long)p * HD, cos_t + (long)p * HD, c0);
-        *reinterpret_cast<bf16x8*>(&k_lds[lrow * LDS_STRIDE + c0]) = klo[j];
-        *reinterpret_cast<bf16x8*>(&k_lds[lrow * LDS_STRIDE + HALF + c0]) = khi[j];
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < V_ITEMS_PER_THREAD; ++j) {
-      const int idx = threadIdx.x + j * NT;
-      if (idx < 2 * KVB * PER_ROW) {
-        const int row = idx / PER_ROW;
-        const int c8 = (idx % PER_ROW) * 8;
-#pragma unroll
-        for (int e = 0; e < 8; ++e)
-          vt_lds[(c8 + e) * VT_STRIDE + row] = reinterpret_cast<__hip_bfloat16*>(&vreg[j])[e];
-      }
-    }
-  };
-
-  const int n_super = (N + 2 * KVB - 1) / (2 * KVB);  // 64 keys per barrier pair
-  if constexpr (PREFETCH) issue_loads(0);
+  KvStage<L, HD, NT, KVB, false> st;
+  const int n_super = (N + 2 * KVB - 1) / (2 * KVB);
+  if constexpr (PREFETCH) st.issue_loads(lay, in, 0, N);
   for (int kt = 0; kt < n_super; ++kt) {
     const int kbase0 = kt * 2 * KVB;
     __syncthreads();               // compute of tile kt-1 done reading LDS
-    if constexpr (!PREFETCH) issue_loads(kbase0);
-    write_tile(kbase0);            // regs -> LDS (rope applied at write)
+    if constexpr (!PREFETCH) st.issue_loads(lay, in, kbase0, N);
+    st.write_tile(kbase0, N, c, sin_t, cos_t, k_lds, nullptr, vt_lds);
     if constexpr (PREFETCH) {
-      if (kt + 1 < n_super) issue_loads(kbase0 + 2 * KVB);  // fly during compute
+      if (kt + 1 < n_super) st.issue_loads(lay, in, kbase0 + 2 * KVB, N);  // fly during compute
     }
     __syncthreads();
 
-   constexpr int SUBK = 32;  // keys per MFMA tile (fixed by the 32x32 MFMA)
-   for (int sub = 0; sub < (2 * KVB) / SUBK && kbase0 + sub * SUBK < N; ++sub) {
-    const int kbase = kbase0 + sub * SUBK;
-    const int krow_off = sub * SUBK;
+    for (int sub = 0; sub < (2 * KVB) / SUBK && kbase0 + sub * SUBK < N; ++sub) {
+      const int kbase = kbase0 + sub * SUBK;
+      const int krow_off = sub * SUBK;
 
-    f32x16 s_acc = {};
+      // S^T tile = K @ Q^T : C[k row, q col]
+      f32x16 s_acc = {};
 #pragma unroll
-    for (int s = 0; s < KSLICES; ++s) {
-      bf16x8 af = load8(&k_lds[(krow_off + l31) * LDS_STRIDE + s * 16 + hhalf * 8]);
-      bf16x8 qs;
-      if constexpr (QLDS) qs = load8(&q_lds[(s * 64 + lane) * 8]);
-      else qs = qf[s];
-      s_acc = MFMA32(af, qs, s_acc);
-    }
-    float sv[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int krow = kbase + c_row(r, hhalf);
-      sv[r] = (krow < N) ? s_acc[r] * scale : -INFINITY;
-    }
-    float tmax = sv[0];
-#pragma unroll
-    for (int r = 1; r < 16; ++r) tmax = fmaxf(tmax, sv[r]);
-    tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-    const float m_new = fmaxf(m_run, tmax);
-    const float alpha = (m_run == -INFINITY) ? 0.f : __expf(m_run - m_new);
-    float psum = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      sv[r] = __expf(sv[r] - m_new);
-      psum += sv[r];
-    }
-    psum += __shfl_xor(psum, 32, 64);
-    l_run = l_run * alpha + psum;
-    m_run = m_new;
-#pragma unroll
-    for (int t = 0; t < DTILES; ++t)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) o_acc[t][r] *= alpha;
-
-    bf16x8 p0 = pack_fragment(sv, 0);
-    bf16x8 p1 = pack_fragment(sv, 8);
-#pragma unroll
-    for (int t = 0; t < DTILES; ++t) {
-      bf16x8 a0 = load8(&vt_lds[(t * 32 + l31) * VT_STRIDE + krow_off + hhalf * 8]);
-      bf16x8 a1 = load8(&vt_lds[(t * 32 + l31) * VT_STRIDE + krow_off + 16 + hhalf * 8]);
-      f32x16 acc;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[r] = o_acc[t][r];
-      acc = MFMA32(a0, p0, acc);
-      acc = MFMA32(a1, p1, acc);
-#pragma unroll
-      for (int r = 0; r < 16; ++r) o_acc[t][r] = acc[r];
-    }
-   }
-  }
-
-  const float inv_l = 1.0f / l_run;
-  const int qrow = q0 + l31;
-  if (qrow < N) {
-    // O token-major: ((b*N + n)*H + h)*hd + d
-    __hip_bfloat16* op = o + (((long)b * N + qrow) * H + h) * HD;
-#pragma unroll
-    for (int t = 0; t < DTILES; ++t)
+      for (int s = 0; s < KSLICES; ++s) {
+        bf16x8 af = load8(&k_lds[(krow_off + l31) * LDS_STRIDE + s * 16 + hhalf * 8]);
+        bf16x8 qs;
+        if constexpr (QLDS) qs = load8(&q_lds[(s * 64 + c.lane) * 8]);
+        else qs = qf[s];
+        s_acc = MFMA32(af, qs, s_acc);
+      }
+      float sv[16];
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int d = t * 32 + c_row(r, hhalf);
-        *reinterpret_cast<short*>(op + d) = f32_to_bf16(o_acc[t][r] * inv_l);
+        const int krow = kbase + c_row(r, hhalf);
+        sv[r] = (krow < N) ? s_acc[r] * scale : -INFINITY;
       }
-    if (hhalf == 0) lse[((long)b * H + h) * N + qrow] = m_run + __logf(l_run);
+      // online softmax: row (q) stats over this tile's 32 k
+      float tmax = sv[0];
+#pragma unroll
+      for (int r = 1; r < 16; ++r) tmax = fmaxf(tmax, sv[r]);
+      tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
+      const float m_new = fmaxf(m_run, tmax);
+      const float alpha = (m_run == -INFINITY) ? 0.f : __expf(m_run - m_new);
+      float psum = 0.f;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        sv[r] = __expf(sv[r] - m_new);
+        psum += sv[r];
+      }
+      psum += __shfl_xor(psum, 32, 64);
+      l_run = l_run * alpha + psum;
+      m_run = m_new;
+#pragma unroll
+      for (int t = 0; t < DTILES; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o_acc[t][r] *= alpha;
+
+      // PV: O^T[d, q] += V^T[d, k] @ P^T[k, q]
+      bf16x8 p0 = pack_fragment(sv, 0);
+      bf16x8 p1 = pack_fragment(sv, 8);
+#pragma unroll
+      for (int t = 0; t < DTILES; ++t) {
+        const __hip_bfloat16* vt = &vt_lds[(t * 32 + l31) * VT_STRIDE + krow_off + hhalf * 8];
+        mfma2_acc(o_acc[t], load8(vt), p0, load8(vt + 16), p1);
+      }
+    }
+  }
+
+  // epilogue: O[q, d] = O^T / l ; lse = m + log(l)
+  if (qrow < N) {
+    store_rows_bf16(lay.o_row(o, qrow), o_acc, hhalf, 1.0f / l_run);
+    if (hhalf == 0) lse[c.stat_off + qrow] = m_run + __logf(l_run);
   }
 }
 
 // ---------------------------------------------------------------------------
-// Backward dQ
+// Backward dQ: per q block, loop over kv tiles.
+//   S^T = K @ Q^T (recompute) ; P^T = exp(S^T*scale - lse[q])
+//   dP^T[k,q] = V @ dO^T       ; dS^T = P^T * (dP^T - D[q]) * scale
+//   dQ^T[d,q] += K^T[d,k-slice] @ pack(dS^T)
 // ---------------------------------------------------------------------------
-template <int HD, int NT = 256, int MINW = 1, int KVB = 32>
+template <int HD, int KVB>
+struct DqSmem {  // k_lds (rope'd K) | v_lds | kt_lds (rope'd K^T)
+  using Tile = KvTile<HD, KVB>;
+  static constexpr int V_OFF = Tile::TILE;
+  static constexpr int KT_OFF = 2 * Tile::TILE;
+  static constexpr size_t BYTES = (KT_OFF + Tile::T_TILE) * sizeof(__hip_bfloat16);
+};
+
+template <class L, int HD, int NT = 256, int MINW = 1, int KVB = 32>
 __global__ __launch_bounds__(NT, MINW) void bwd_dq_kernel(
-    const __hip_bfloat16* __restrict__ qkv, const __hip_bfloat16* __restrict__ dout,
+    typename L::Qkv in, const __hip_bfloat16* __restrict__ dout,
     const float* __restrict__ sin_t, const float* __restrict__ cos_t,
-    const float* __restrict__ lse, const float* __restrict__ D,
-    __hip_bfloat16* __restrict__ dqkv, int B, int H, int N, int P, float scale) {
+    const float* __restrict__ lse, const float* __restrict__ D, typename L::DQkv grad, int B,
+    int H, int N, int P, float scale) {
+  using Smem = DqSmem<HD, KVB>;
   constexpr int KSLICES = HD / 16;
   constexpr int DTILES = HD / 32;
-  constexpr int LDS_STRIDE = HD + 8;
-  constexpr int KT_STRIDE = 2 * KVB + 8;
-  constexpr int HALF = HD / 2;
+  constexpr int LDS_STRIDE = Smem::Tile::LDS_STRIDE;
+  constexpr int KT_STRIDE = Smem::Tile::T_STRIDE;
 
-  const int bh = blockIdx.x;
-  const int b = bh / H;
-  const int h = bh % H;
-  const int wave = threadIdx.x / 64;
-  const int lane = threadIdx.x & 63;
-  const int hhalf = lane >> 5;
-  const int l31 = lane & 31;
-  const int q0 = blockIdx.y * (NT / 2) + wave * 32;
-  const int prefix = N - P;
-  const bool use_rope = (sin_t != nullptr);
-
-  QkvView qv;
-  qv.base = qkv + ((long)b * N * 3 * H + h) * HD;
-  qv.row_stride = (long)3 * H * HD;
-  qv.which_stride = (long)H * HD;
-  const __hip_bfloat16* do_base = dout + ((long)b * N * H + h) * HD;  // token-major dO
-  const long do_stride = (long)H * HD;
+  const BlockCtx c = block_ctx(H, N, P, sin_t);
+  const L lay(c.b, c.h, H, N, HD);
+  const int hhalf = c.hhalf, l31 = c.l31;
+  const int q0 = blockIdx.y * (NT / 2) + c.wave * 32;
 
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  __hip_bfloat16* k_lds = reinterpret_cast<__hip_bfloat16*>(smem_raw);   // rope'd K
-  __hip_bfloat16* v_lds = k_lds + 2 * KVB * LDS_STRIDE;
-  __hip_bfloat16* kt_lds = v_lds + 2 * KVB * LDS_STRIDE;                  // rope'd K^T
+  __hip_bfloat16* k_lds = reinterpret_cast<__hip_bfloat16*>(smem_raw);
+  __hip_bfloat16* v_lds = k_lds + Smem::V_OFF;
+  __hip_bfloat16* kt_lds = k_lds + Smem::KT_OFF;
 
   const int qrow = q0 + l31;
   const int safe = qrow < N ? qrow : (N - 1);
   bf16x8 qf[KSLICES], dof[KSLICES];
-  {
 #pragma unroll
-    for (int s = 0; s < KSLICES; ++s) {
-      qf[s] = load8(qv.at(safe, 0, s * 16 + hhalf * 8));
-      dof[s] = load8(do_base + (long)safe * do_stride + s * 16 + hhalf * 8);
-    }
-    const int p = safe - prefix;
-    if (use_rope && p >= 0) {
-      const float* srow = sin_t + (long)p * HD;
-      const float* crow = cos_t + (long)p * HD;
-#pragma unroll
-      for (int s2 = 0; s2 < KSLICES / 2; ++s2)
-        rope_rotate8(qf[s2], qf[s2 + KSLICES / 2], srow, crow, s2 * 16 + hhalf * 8);
-    }
+  for (int s = 0; s < KSLICES; ++s) {
+    qf[s] = load8(lay.at(in, safe, 0, s * 16 + hhalf * 8));
+    dof[s] = load8(lay.o_row(dout, safe) + s * 16 + hhalf * 8);
   }
-  const float my_lse = lse[((long)b * H + h) * N + safe];
-  const float my_D = D[((long)b * H + h) * N + safe];
+  rope_fragments(qf, sin_t, cos_t, safe, c);
+  const float my_lse = lse[c.stat_off + safe];
+  const float my_D = D[c.stat_off + safe];
 
   float dq_acc[DTILES][16];
 #pragma unroll
@@ -383,209 +458,117 @@ __global__ __launch_bounds__(NT, MINW) void bwd_dq_kernel(
 #pragma unroll
     for (int r = 0; r < 16; ++r) dq_acc[t][r] = 0.f;
 
-  constexpr int PAIRS_PER_ROW = HALF / 8;
-  constexpr int PER_ROW = HD / 8;
-  constexpr int K_ITEMS = 2 * KVB * PAIRS_PER_ROW;
-  constexpr int K_IPT = (K_ITEMS + NT - 1) / NT;
-  constexpr int V_IPT = (2 * KVB * PER_ROW + NT - 1) / NT;
-  bf16x8 klo[K_IPT], khi[K_IPT], vreg[V_IPT];
-  auto issue_loads = [&](int kbase0) {
-#pragma unroll
-    for (int j = 0; j < K_IPT; ++j) {
-      const int item = threadIdx.x + j * NT;
-      const int krow = kbase0 + item / PAIRS_PER_ROW;
-      const int c0 = (item % PAIRS_PER_ROW) * 8;
-      const bool ok = item < K_ITEMS && krow < N;
-      klo[j] = ok ? load8(qv.at(krow, 1, c0)) : bf16x8{};
-      khi[j] = ok ? load8(qv.at(krow, 1, c0 + HALF)) : bf16x8{};
-    }
-#pragma unroll
-    for (int j = 0; j < V_IPT; ++j) {
-      const int idx = threadIdx.x + j * NT;
-      const int krow = kbase0 + idx / PER_ROW;
-      vreg[j] = (idx < 2 * KVB * PER_ROW && krow < N)
-                    ? load8(qv.at(krow, 2, (idx % PER_ROW) * 8)) : bf16x8{};
-    }
-  };
-  auto write_tile = [&](int kbase0) {
-#pragma unroll
-    for (int j = 0; j < K_IPT; ++j) {
-      const int item = threadIdx.x + j * NT;
-      if (item < K_ITEMS) {
-        const int lrow = item / PAIRS_PER_ROW;
-        const int c0 = (item % PAIRS_PER_ROW) * 8;
-        const int krow = kbase0 + lrow;
-        const int p = krow - prefix;
-        if (use_rope && krow < N && p >= 0)
-          rope_rotate8(klo[j], khi[j], sin_t + (long)p * HD, cos_t + (long)p * HD, c0);
-        *reinterpret_cast<bf16x8*>(&k_lds[lrow * LDS_STRIDE + c0]) = klo[j];
-        *reinterpret_cast<bf16x8*>(&k_lds[lrow * LDS_STRIDE + HALF + c0]) = khi[j];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          kt_lds[(c0 + e) * KT_STRIDE + lrow] = reinterpret_cast<__hip_bfloat16*>(&klo[j])[e];
-          kt_lds[(c0 + HALF + e) * KT_STRIDE + lrow] = reinterpret_cast<__hip_bfloat16*>(&khi[j])[e];
-        }
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < V_IPT; ++j) {
-      const int idx = threadIdx.x + j * NT;
-      if (idx < 2 * KVB * PER_ROW)
-        *reinterpret_cast<bf16x8*>(&v_lds[(idx / PER_ROW) * LDS_STRIDE + (idx % PER_ROW) * 8]) = vreg[j];
-    }
-  };
-
+  KvStage<L, HD, NT, KVB, true> st;
   const int n_super = (N + 2 * KVB - 1) / (2 * KVB);
-  issue_loads(0);
+  st.issue_loads(lay, in, 0, N);
   for (int kt = 0; kt < n_super; ++kt) {
     const int kbase0 = kt * 2 * KVB;
     __syncthreads();
-    write_tile(kbase0);
-    if (kt + 1 < n_super) issue_loads(kbase0 + 2 * KVB);
+    st.write_tile(kbase0, N, c, sin_t, cos_t, k_lds, v_lds, kt_lds);
+    if (kt + 1 < n_super) st.issue_loads(lay, in, kbase0 + 2 * KVB, N);
     __syncthreads();
 
-   constexpr int SUBK = 32;  // keys per MFMA tile (fixed by the 32x32 MFMA)
-   for (int sub = 0; sub < (2 * KVB) / SUBK && kbase0 + sub * SUBK < N; ++sub) {
-    const int kbase = kbase0 + sub * SUBK;
-    const int krow_off = sub * SUBK;
-    f32x16 s_acc = {}, dp_acc = {};
+    for (int sub = 0; sub < (2 * KVB) / SUBK && kbase0 + sub * SUBK < N; ++sub) {
+      const int kbase = kbase0 + sub * SUBK;
+      const int krow_off = sub * SUBK;
+      f32x16 s_acc = {}, dp_acc = {};
 #pragma unroll
-    for (int s = 0; s < KSLICES; ++s) {
-      bf16x8 kf = load8(&k_lds[(krow_off + l31) * LDS_STRIDE + s * 16 + hhalf * 8]);
-      bf16x8 vf = load8(&v_lds[(krow_off + l31) * LDS_STRIDE + s * 16 + hhalf * 8]);
-      s_acc = MFMA32(kf, qf[s], s_acc);
-      dp_acc = MFMA32(vf, dof[s], dp_acc);
+      for (int s = 0; s < KSLICES; ++s) {
+        bf16x8 kf = load8(&k_lds[(krow_off + l31) * LDS_STRIDE + s * 16 + hhalf * 8]);
+        bf16x8 vf = load8(&v_lds[(krow_off + l31) * LDS_STRIDE + s * 16 + hhalf * 8]);
+        s_acc = MFMA32(kf, qf[s], s_acc);
+        dp_acc = MFMA32(vf, dof[s], dp_acc);
+      }
+      float ds[16];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int krow = kbase + c_row(r, hhalf);
+        float p = (krow < N && qrow < N) ? __expf(s_acc[r] * scale - my_lse) : 0.f;
+        ds[r] = p * (dp_acc[r] - my_D) * scale;
+      }
+      bf16x8 f0 = pack_fragment(ds, 0);
+      bf16x8 f1 = pack_fragment(ds, 8);
+#pragma unroll
+      for (int t = 0; t < DTILES; ++t) {
+        const __hip_bfloat16* kt_p = &kt_lds[(t * 32 + l31) * KT_STRIDE + krow_off + hhalf * 8];
+        mfma2_acc(dq_acc[t], load8(kt_p), f0, load8(kt_p + 16), f1);
+      }
     }
-    float ds[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int krow = kbase + c_row(r, hhalf);
-      float p = (krow < N && qrow < N) ? __expf(s_acc[r] * scale - my_lse) : 0.f;
-      ds[r] = p * (dp_acc[r] - my_D) * scale;
-    }
-    bf16x8 f0 = pack_fragment(ds, 0);
-    bf16x8 f1 = pack_fragment(ds, 8);
-#pragma unroll
-    for (int t = 0; t < DTILES; ++t) {
-      bf16x8 a0 = load8(&kt_lds[(t * 32 + l31) * KT_STRIDE + krow_off + hhalf * 8]);
-      bf16x8 a1 = load8(&kt_lds[(t * 32 + l31) * KT_STRIDE + krow_off + 16 + hhalf * 8]);
-      f32x16 acc;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[r] = dq_acc[t][r];
-      acc = MFMA32(a0, f0, acc);
-      acc = MFMA32(a1, f1, acc);
-#pragma unroll
-      for (int r = 0; r < 16; ++r) dq_acc[t][r] = acc[r];
-    }
-   }
   }
 
   if (qrow < N) {
-    // inverse rope on dQ: pairs (d, d+HALF) = (tile t, tile t+DTILES/2) reg r
-    const int p = qrow - prefix;
-    if (use_rope && p >= 0) {
-      const float* srow = sin_t + (long)p * HD;
-      const float* crow = cos_t + (long)p * HD;
-#pragma unroll
-      for (int t = 0; t < DTILES / 2; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int d = t * 32 + c_row(r, hhalf);
-          const float c = crow[d], s = srow[d];
-          const float glo = dq_acc[t][r], ghi = dq_acc[t + DTILES / 2][r];
-          dq_acc[t][r] = glo * c + ghi * s;
-          dq_acc[t + DTILES / 2][r] = ghi * c - glo * s;
-        }
-    }
-    __hip_bfloat16* dqp = dqkv + ((((long)b * N + qrow) * 3 + 0) * H + h) * HD;
-#pragma unroll
-    for (int t = 0; t < DTILES; ++t)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int d = t * 32 + c_row(r, hhalf);
-        *reinterpret_cast<short*>(dqp + d) = f32_to_bf16(dq_acc[t][r]);
-      }
+    rope_inverse(dq_acc, sin_t, cos_t, qrow, c);
+    store_rows_bf16(lay.grad_row(grad, 0, qrow), dq_acc, hhalf);
   }
 }
 
 // ---------------------------------------------------------------------------
-// Backward dK/dV
+// Backward dK/dV: per kv block of 32 rows per wave, loop over 32-row q tiles,
+// SQB (32 or 64) q rows staged per barrier pair.
+//   S[q,k] = Q @ K^T (C: rows=q, cols=k; K wave-resident as B)
+//   P = exp(S*scale - lse[q]); dP[q,k] = dO @ V^T ; dS = P*(dP - D[q])*scale
+// pack_fragment of a C tile (rows=q, cols=k) is the B layout of P / dS, so
+//   dV^T[d, k] += dO^T[d, q] @ P[q, k] ; dK^T[d, k] += Q^T[d, q] @ dS[q, k]
+// with dO^T / Q^T as A from the transposed LDS tiles.
 // ---------------------------------------------------------------------------
-// MODE splits the kernel for register-starved configs (hd-128 holds 366
-// regs with both accumulator sets -> occupancy 1): MODE=1 computes only dV
-// (no vf/dP/dK state), MODE=2 only dK. Each re-streams Q/dO, but at 2
-// waves/SIMD instead of 1 the latency hiding more than pays for it.
-template <int HD, int NT = 256, int MINW = 1, int MODE = 0>
+template <int HD, int SQB>
+struct DkvSmem {  // qt_lds (rope'd Q^T) | dot_lds (dO^T) | lse [SQB] | D [SQB]
+  static constexpr int QB = 32;              // q rows per MFMA tile
+  static constexpr int QT_STRIDE = SQB + 8;  // column stride, sized for the SQB staged rows
+  static constexpr int DOT_OFF = HD * QT_STRIDE;
+  static constexpr int STAT_OFF = 2 * HD * QT_STRIDE;  // in bf16 elements
+  static constexpr size_t BYTES = STAT_OFF * sizeof(__hip_bfloat16) + 2 * SQB * sizeof(float);
+};
+
+template <class L, int HD, int NT = 256, int MINW = 1, int SQB = 32>
 __global__ __launch_bounds__(NT, MINW) void bwd_dkv_kernel(
-    const __hip_bfloat16* __restrict__ qkv, const __hip_bfloat16* __restrict__ dout,
+    typename L::Qkv in, const __hip_bfloat16* __restrict__ dout,
     const float* __restrict__ sin_t, const float* __restrict__ cos_t,
-    const float* __restrict__ lse, const float* __restrict__ D,
-    __hip_bfloat16* __restrict__ dqkv, int B, int H, int N, int P, float scale) {
+    const float* __restrict__ lse, const float* __restrict__ D, typename L::DQkv grad, int B,
+    int H, int N, int P, float scale) {
+  using Smem = DkvSmem<HD, SQB>;
   constexpr int KSLICES = HD / 16;
   constexpr int DTILES = HD / 32;
-  constexpr int QB = 32;
-  constexpr int QT_STRIDE = QB + 8;
+  constexpr int QB = Smem::QB;
+  constexpr int QT_STRIDE = Smem::QT_STRIDE;
   constexpr int HALF = HD / 2;
 
-  const int bh = blockIdx.x;
-  const int b = bh / H;
-  const int h = bh % H;
-  const int wave = threadIdx.x / 64;
-  const int lane = threadIdx.x & 63;
-  const int hhalf = lane >> 5;
-  const int l31 = lane & 31;
-  const int k0 = blockIdx.y * 128 + wave * 32;
-  const int prefix = N - P;
-  const bool use_rope = (sin_t != nullptr);
-
-  QkvView qv;
-  qv.base = qkv + ((long)b * N * 3 * H + h) * HD;
-  qv.row_stride = (long)3 * H * HD;
-  qv.which_stride = (long)H * HD;
-  const __hip_bfloat16* do_base = dout + ((long)b * N * H + h) * HD;
-  const long do_stride = (long)H * HD;
+  const BlockCtx c = block_ctx(H, N, P, sin_t);
+  const L lay(c.b, c.h, H, N, HD);
+  const int hhalf = c.hhalf, l31 = c.l31;
+  const int k0 = blockIdx.y * 128 + c.wave * 32;
 
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  __hip_bfloat16* qt_lds = reinterpret_cast<__hip_bfloat16*>(smem_raw);  // rope'd Q^T
-  __hip_bfloat16* dot_lds = qt_lds + HD * QT_STRIDE;                      // dO^T
-  float* lse_lds = reinterpret_cast<float*>(dot_lds + HD * QT_STRIDE);
-  float* d_lds = lse_lds + QB;
+  __hip_bfloat16* qt_lds = reinterpret_cast<__hip_bfloat16*>(smem_raw);
+  __hip_bfloat16* dot_lds = qt_lds + Smem::DOT_OFF;
+  float* lse_lds = reinterpret_cast<float*>(qt_lds + Smem::STAT_OFF);
+  float* d_lds = lse_lds + SQB;
 
   const int krow = k0 + l31;
   const int safe = krow < N ? krow : (N - 1);
-  bf16x8 kf[KSLICES], vf[MODE == 1 ? 1 : KSLICES];
-  {
+  bf16x8 kf[KSLICES], vf[KSLICES];
 #pragma unroll
-    for (int s = 0; s < KSLICES; ++s) {
-      kf[s] = load8(qv.at(safe, 1, s * 16 + hhalf * 8));
-      if constexpr (MODE != 1) vf[s] = load8(qv.at(safe, 2, s * 16 + hhalf * 8));
-    }
-    const int p = safe - prefix;
-    if (use_rope && p >= 0) {
-      const float* srow = sin_t + (long)p * HD;
-      const float* crow = cos_t + (long)p * HD;
-#pragma unroll
-      for (int s2 = 0; s2 < KSLICES / 2; ++s2)
-        rope_rotate8(kf[s2], kf[s2 + KSLICES / 2], srow, crow, s2 * 16 + hhalf * 8);
-    }
+  for (int s = 0; s < KSLICES; ++s) {
+    kf[s] = load8(lay.at(in, safe, 1, s * 16 + hhalf * 8));
+    vf[s] = load8(lay.at(in, safe, 2, s * 16 + hhalf * 8));
   }
+  rope_fragments(kf, sin_t, cos_t, safe, c);
 
-  float dk_acc[MODE == 1 ? 1 : DTILES][16], dv_acc[MODE == 2 ? 1 : DTILES][16];
+  float dk_acc[DTILES][16], dv_acc[DTILES][16];
 #pragma unroll
   for (int t = 0; t < DTILES; ++t)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      if constexpr (MODE != 1) dk_acc[t][r] = 0.f;
-      if constexpr (MODE != 2) dv_acc[t][r] = 0.f;
+      dk_acc[t][r] = 0.f;
+      dv_acc[t][r] = 0.f;
     }
 
   constexpr int PAIRS_PER_ROW = HALF / 8;
   constexpr int PER_ROW = HD / 8;
-  constexpr int QK_ITEMS = QB * PAIRS_PER_ROW;   // <= 256
-  constexpr int DO_ITEMS = QB * PER_ROW;         // <= 512
+  constexpr int QK_ITEMS = SQB * PAIRS_PER_ROW;
+  constexpr int DO_ITEMS = SQB * PER_ROW;
   // QK_ITEMS can exceed NT (HD=128, NT=128 -> 256 items): loop like the
-  // dO staging. QK_IPT==1 for every other variant, so those paths are
-  // unchanged. (Single-shot staging here silently dropped half the Q tile
+  // dO staging. (Single-shot staging here silently dropped half the Q tile
   // for hd-128 small-N — caught by tests/test_kernel_layouts.py.)
   constexpr int QK_IPT = (QK_ITEMS + NT - 1) / NT;
   constexpr int DO_IPT = (DO_ITEMS + NT - 1) / NT;
@@ -598,21 +581,20 @@ __global__ __launch_bounds__(NT, MINW) void bwd_dkv_kernel(
       const int qrow = qbase0 + idx / PAIRS_PER_ROW;
       const int c0 = (idx % PAIRS_PER_ROW) * 8;
       const bool ok = idx < QK_ITEMS && qrow < N;
-      qlo[j] = ok ? load8(qv.at(qrow, 0, c0)) : bf16x8{};
-      qhi[j] = ok ? load8(qv.at(qrow, 0, c0 + HALF)) : bf16x8{};
+      qlo[j] = ok ? load8(lay.at(in, qrow, 0, c0)) : bf16x8{};
+      qhi[j] = ok ? load8(lay.at(in, qrow, 0, c0 + HALF)) : bf16x8{};
     }
 #pragma unroll
     for (int j = 0; j < DO_IPT; ++j) {
       const int idx = threadIdx.x + j * NT;
       const int qrow = qbase0 + idx / PER_ROW;
-      doreg[j] = (idx < DO_ITEMS && qrow < N)
-                     ? load8(do_base + (long)qrow * do_stride + (idx % PER_ROW) * 8)
-                     : bf16x8{};
+      doreg[j] = (idx < DO_ITEMS && qrow < N) ? load8(lay.o_row(dout, qrow) + (idx % PER_ROW) * 8)
+                                              : bf16x8{};
     }
-    if (threadIdx.x < QB) {
+    if (threadIdx.x < SQB) {
       const int qrow = qbase0 + threadIdx.x;
-      lse_reg = (qrow < N) ? lse[((long)b * H + h) * N + qrow] : INFINITY;
-      d_reg = (qrow < N) ? D[((long)b * H + h) * N + qrow] : 0.f;
+      lse_reg = (qrow < N) ? lse[c.stat_off + qrow] : INFINITY;
+      d_reg = (qrow < N) ? D[c.stat_off + qrow] : 0.f;
     }
   };
   auto write_tile = [&](int qbase0) {
@@ -623,8 +605,8 @@ __global__ __launch_bounds__(NT, MINW) void bwd_dkv_kernel(
         const int lrow = idx / PAIRS_PER_ROW;
         const int c0 = (idx % PAIRS_PER_ROW) * 8;
         const int qrow = qbase0 + lrow;
-        const int p = qrow - prefix;
-        if (use_rope && qrow < N && p >= 0)
+        const int p = qrow - c.prefix;
+        if (c.use_rope && qrow < N && p >= 0)
           rope_rotate8(qlo[j], qhi[j], sin_t + (long)p * HD, cos_t + (long)p * HD, c0);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
@@ -644,294 +626,31 @@ __global__ __launch_bounds__(NT, MINW) void bwd_dkv_kernel(
           dot_lds[(c8 + e) * QT_STRIDE + lrow] = reinterpret_cast<__hip_bfloat16*>(&doreg[j])[e];
       }
     }
-    if (threadIdx.x < QB) {
+    if (threadIdx.x < SQB) {
       lse_lds[threadIdx.x] = lse_reg;
       d_lds[threadIdx.x] = d_reg;
     }
   };
 
-  const int n_q = (N + QB - 1) / QB;
+  const int n_q = (N + SQB - 1) / SQB;
   issue_loads(0);
   for (int qt = 0; qt < n_q; ++qt) {
-    const int qbase0 = qt * QB;
-    __syncthreads();
-    write_tile(qbase0);
-    if (qt + 1 < n_q) issue_loads(qbase0 + QB);
-    __syncthreads();
-
-   {
-    const int qbase = qbase0;
-    const int qrow_off = 0;
-    f32x16 s_acc = {}, dp_acc = {};
-#pragma unroll
-    for (int s = 0; s < KSLICES; ++s) {
-      union { unsigned u[4]; bf16x8 v8; } aq, ad;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const int d = s * 16 + hhalf * 8 + e;
-        reinterpret_cast<__hip_bfloat16*>(&aq)[e] = qt_lds[d * QT_STRIDE + qrow_off + l31];
-        if constexpr (MODE != 1)
-          reinterpret_cast<__hip_bfloat16*>(&ad)[e] = dot_lds[d * QT_STRIDE + qrow_off + l31];
-      }
-      s_acc = MFMA32(aq.v8, kf[s], s_acc);
-      if constexpr (MODE != 1) dp_acc = MFMA32(ad.v8, vf[s], dp_acc);
-    }
-    float pv[16], ds[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int qrow = qbase + c_row(r, hhalf);
-      const bool valid = (qrow < N) && (krow < N);
-      const float l = lse_lds[qrow_off + c_row(r, hhalf)];
-      float p = valid ? __expf(s_acc[r] * scale - l) : 0.f;
-      pv[r] = p;
-      if constexpr (MODE != 1)
-        ds[r] = p * (dp_acc[r] - d_lds[qrow_off + c_row(r, hhalf)]) * scale;
-    }
-    bf16x8 p0, p1, s0, s1;
-    if constexpr (MODE != 2) {
-      p0 = pack_fragment(pv, 0);
-      p1 = pack_fragment(pv, 8);
-    }
-    if constexpr (MODE != 1) {
-      s0 = pack_fragment(ds, 0);
-      s1 = pack_fragment(ds, 8);
-    }
-#pragma unroll
-    for (int t = 0; t < DTILES; ++t) {
-      union { unsigned u[4]; bf16x8 v8; } ado0, ado1, aq0, aq1;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        if constexpr (MODE != 2) {
-          reinterpret_cast<__hip_bfloat16*>(&ado0)[e] = dot_lds[(t * 32 + l31) * QT_STRIDE + qrow_off + hhalf * 8 + e];
-          reinterpret_cast<__hip_bfloat16*>(&ado1)[e] = dot_lds[(t * 32 + l31) * QT_STRIDE + qrow_off + 16 + hhalf * 8 + e];
-        }
-        if constexpr (MODE != 1) {
-          reinterpret_cast<__hip_bfloat16*>(&aq0)[e] = qt_lds[(t * 32 + l31) * QT_STRIDE + qrow_off + hhalf * 8 + e];
-          reinterpret_cast<__hip_bfloat16*>(&aq1)[e] = qt_lds[(t * 32 + l31) * QT_STRIDE + qrow_off + 16 + hhalf * 8 + e];
-        }
-      }
-      if constexpr (MODE != 2) {
-        f32x16 accv;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) accv[r] = dv_acc[t][r];
-        accv = MFMA32(ado0.v8, p0, accv);
-        accv = MFMA32(ado1.v8, p1, accv);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) dv_acc[t][r] = accv[r];
-      }
-      if constexpr (MODE != 1) {
-        f32x16 acck;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acck[r] = dk_acc[t][r];
-        acck = MFMA32(aq0.v8, s0, acck);
-        acck = MFMA32(aq1.v8, s1, acck);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) dk_acc[t][r] = acck[r];
-      }
-    }
-   }
-  }
-
-  if (krow < N) {
-    const int p = krow - prefix;
-    if constexpr (MODE != 1) {
-      if (use_rope && p >= 0) {
-        const float* srow = sin_t + (long)p * HD;
-        const float* crow = cos_t + (long)p * HD;
-#pragma unroll
-        for (int t = 0; t < DTILES / 2; ++t)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int d = t * 32 + c_row(r, hhalf);
-            const float c = crow[d], s = srow[d];
-            const float glo = dk_acc[t][r], ghi = dk_acc[t + DTILES / 2][r];
-            dk_acc[t][r] = glo * c + ghi * s;
-            dk_acc[t + DTILES / 2][r] = ghi * c - glo * s;
-          }
-      }
-    }
-    __hip_bfloat16* dkp = dqkv + ((((long)b * N + krow) * 3 + 1) * H + h) * HD;
-    __hip_bfloat16* dvp = dqkv + ((((long)b * N + krow) * 3 + 2) * H + h) * HD;
-#pragma unroll
-    for (int t = 0; t < DTILES; ++t)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int d = t * 32 + c_row(r, hhalf);
-        if constexpr (MODE != 1)
-          *reinterpret_cast<short*>(dkp + d) = f32_to_bf16(dk_acc[t][r]);
-        if constexpr (MODE != 2)
-          *reinterpret_cast<short*>(dvp + d) = f32_to_bf16(dv_acc[t][r]);
-      }
-  }
-}
-
-// ---------------------------------------------------------------------------
-// Backward dK/dV, 64-row super-tile variant (gated: DINOV3_FMHA_DKV64=1).
-//
-// Stages TWO 32-row q-tiles per barrier pair (half the __syncthreads and
-// lse/D loads of bwd_dkv_kernel). The round-1 attempt of this NaN'd because
-// the 64 staged rows kept the 32-row column stride (QB+8=40): rows 40..63 of
-// every d-column overwrote the next column, and lse/d overlapped (d_lds was
-// offset by QB). Fixed here: QT_STRIDE = 2*QB+8 = 72 and 2*QB-sized lse/d —
-// matching the stride the fwd/dq kernels already use. Validate on hardware
-// (tests/test_fmha_rope_gpu.py::test_dkv64_variant) before enabling.
-// ---------------------------------------------------------------------------
-template <int HD, int NT = 256, int MODE = 0>
-__global__ __launch_bounds__(NT) void bwd_dkv64_kernel(
-    const __hip_bfloat16* __restrict__ qkv, const __hip_bfloat16* __restrict__ dout,
-    const float* __restrict__ sin_t, const float* __restrict__ cos_t,
-    const float* __restrict__ lse, const float* __restrict__ D,
-    __hip_bfloat16* __restrict__ dqkv, int B, int H, int N, int P, float scale) {
-  constexpr int KSLICES = HD / 16;
-  constexpr int DTILES = HD / 32;
-  constexpr int QB = 32;
-  constexpr int SQB = 2 * QB;            // staged rows per barrier pair
-  constexpr int QT_STRIDE = SQB + 8;     // 72: column stride sized for SQB rows
-  constexpr int HALF = HD / 2;
-
-  const int bh = blockIdx.x;
-  const int b = bh / H;
-  const int h = bh % H;
-  const int wave = threadIdx.x / 64;
-  const int lane = threadIdx.x & 63;
-  const int hhalf = lane >> 5;
-  const int l31 = lane & 31;
-  const int k0 = blockIdx.y * 128 + wave * 32;
-  const int prefix = N - P;
-  const bool use_rope = (sin_t != nullptr);
-
-  QkvView qv;
-  qv.base = qkv + ((long)b * N * 3 * H + h) * HD;
-  qv.row_stride = (long)3 * H * HD;
-  qv.which_stride = (long)H * HD;
-  const __hip_bfloat16* do_base = dout + ((long)b * N * H + h) * HD;
-  const long do_stride = (long)H * HD;
-
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  __hip_bfloat16* qt_lds = reinterpret_cast<__hip_bfloat16*>(smem_raw);  // rope'd Q^T [HD][72]
-  __hip_bfloat16* dot_lds = qt_lds + HD * QT_STRIDE;                     // dO^T [HD][72]
-  float* lse_lds = reinterpret_cast<float*>(dot_lds + HD * QT_STRIDE);   // [SQB]
-  float* d_lds = lse_lds + SQB;                                          // [SQB]
-
-  const int krow = k0 + l31;
-  const int safe = krow < N ? krow : (N - 1);
-  bf16x8 kf[KSLICES], vf[MODE == 1 ? 1 : KSLICES];
-  {
-#pragma unroll
-    for (int s = 0; s < KSLICES; ++s) {
-      kf[s] = load8(qv.at(safe, 1, s * 16 + hhalf * 8));
-      if constexpr (MODE != 1) vf[s] = load8(qv.at(safe, 2, s * 16 + hhalf * 8));
-    }
-    const int p = safe - prefix;
-    if (use_rope && p >= 0) {
-      const float* srow = sin_t + (long)p * HD;
-      const float* crow = cos_t + (long)p * HD;
-#pragma unroll
-      for (int s2 = 0; s2 < KSLICES / 2; ++s2)
-        rope_rotate8(kf[s2], kf[s2 + KSLICES / 2], srow, crow, s2 * 16 + hhalf * 8);
-    }
-  }
-
-  float dk_acc[MODE == 1 ? 1 : DTILES][16], dv_acc[MODE == 2 ? 1 : DTILES][16];
-#pragma unroll
-  for (int t = 0; t < DTILES; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      if constexpr (MODE != 1) dk_acc[t][r] = 0.f;
-      if constexpr (MODE != 2) dv_acc[t][r] = 0.f;
-    }
-
-  constexpr int PAIRS_PER_ROW = HALF / 8;
-  constexpr int PER_ROW = HD / 8;
-  constexpr int QK_ITEMS = SQB * PAIRS_PER_ROW;  // up to 512 (HD=128)
-  constexpr int DO_ITEMS = SQB * PER_ROW;        // up to 1024 (HD=128)
-  constexpr int QK_IPT = (QK_ITEMS + NT - 1) / NT;
-  constexpr int DO_IPT = (DO_ITEMS + NT - 1) / NT;
-  bf16x8 qlo[QK_IPT], qhi[QK_IPT], doreg[DO_IPT];
-  float lse_reg = INFINITY, d_reg = 0.f;
-  auto issue_loads = [&](int qbase0) {
-#pragma unroll
-    for (int j = 0; j < QK_IPT; ++j) {
-      const int idx = threadIdx.x + j * NT;
-      const int qrow = qbase0 + idx / PAIRS_PER_ROW;
-      const int c0 = (idx % PAIRS_PER_ROW) * 8;
-      const bool ok = idx < QK_ITEMS && qrow < N;
-      qlo[j] = ok ? load8(qv.at(qrow, 0, c0)) : bf16x8{};
-      qhi[j] = ok ? load8(qv.at(qrow, 0, c0 + HALF)) : bf16x8{};
-    }
-#pragma unroll
-    for (int j = 0; j < DO_IPT; ++j) {
-      const int idx = threadIdx.x + j * NT;
-      const int qrow = qbase0 + idx / PER_ROW;
-      doreg[j] = (idx < DO_ITEMS && qrow < N)
-                     ? load8(do_base + (long)qrow * do_stride + (idx % PER_ROW) * 8)
-                     : bf16x8{};
-    }
-    if (threadIdx.x < SQB) {
-      const int qrow = qbase0 + threadIdx.x;
-      lse_reg = (qrow < N) ? lse[((long)b * H + h) * N + qrow] : INFINITY;
-      d_reg = (qrow < N) ? D[((long)b * H + h) * N + qrow] : 0.f;
-    }
-  };
-  auto write_tile = [&](int qbase0) {
-#pragma unroll
-    for (int j = 0; j < QK_IPT; ++j) {
-      const int idx = threadIdx.x + j * NT;
-      if (idx < QK_ITEMS) {
-        const int lrow = idx / PAIRS_PER_ROW;
-        const int c0 = (idx % PAIRS_PER_ROW) * 8;
-        const int qrow = qbase0 + lrow;
-        const int p = qrow - prefix;
-        if (use_rope && qrow < N && p >= 0)
-          rope_rotate8(qlo[j], qhi[j], sin_t + (long)p * HD, cos_t + (long)p * HD, c0);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          qt_lds[(c0 + e) * QT_STRIDE + lrow] = reinterpret_cast<__hip_bfloat16*>(&qlo[j])[e];
-          qt_lds[(c0 + HALF + e) * QT_STRIDE + lrow] = reinterpret_cast<__hip_bfloat16*>(&qhi[j])[e];
-        }
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < DO_IPT; ++j) {
-      const int idx = threadIdx.x + j * NT;
-      if (idx < DO_ITEMS) {
-        const int lrow = idx / PER_ROW;
-        const int c8 = (idx % PER_ROW) * 8;
-#pragma unroll
-        for (int e = 0; e < 8; ++e)
-          dot_lds[(c8 + e) * QT_STRIDE + lrow] = reinterpret_cast<__hip_bfloat16*>(&doreg[j])[e];
-      }
-    }
-    if (threadIdx.x < SQB) {
-      lse_lds[threadIdx.x] = lse_reg;
-      d_lds[threadIdx.x] = d_reg;
-    }
-  };
-
-  const int n_super = (N + SQB - 1) / SQB;
-  issue_loads(0);
-  for (int qt = 0; qt < n_super; ++qt) {
     const int qbase0 = qt * SQB;
     __syncthreads();
     write_tile(qbase0);
-    if (qt + 1 < n_super) issue_loads(qbase0 + SQB);
+    if (qt + 1 < n_q) issue_loads(qbase0 + SQB);
     __syncthreads();
 
-    for (int sub = 0; sub < 2 && qbase0 + sub * QB < N; ++sub) {
+    for (int sub = 0; sub < SQB / QB && (sub == 0 || qbase0 + sub * QB < N); ++sub) {
       const int qbase = qbase0 + sub * QB;
       const int qrow_off = sub * QB;
+      // A fragments Q[q = l31][d] and dO[q = l31][d]: strided reads of Q^T / dO^T
       f32x16 s_acc = {}, dp_acc = {};
 #pragma unroll
       for (int s = 0; s < KSLICES; ++s) {
-        union { unsigned u[4]; bf16x8 v8; } aq, ad;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const int d = s * 16 + hhalf * 8 + e;
-          reinterpret_cast<__hip_bfloat16*>(&aq)[e] = qt_lds[d * QT_STRIDE + qrow_off + l31];
-          reinterpret_cast<__hip_bfloat16*>(&ad)[e] = dot_lds[d * QT_STRIDE + qrow_off + l31];
-        }
-        s_acc = MFMA32(aq.v8, kf[s], s_acc);
-        dp_acc = MFMA32(ad.v8, vf[s], dp_acc);
+        const int d0 = (s * 16 + hhalf * 8) * QT_STRIDE + qrow_off + l31;
+        s_acc = MFMA32(gather8(qt_lds + d0, QT_STRIDE), kf[s], s_acc);
+        dp_acc = MFMA32(gather8(dot_lds + d0, QT_STRIDE), vf[s], dp_acc);
       }
       float pv[16], ds[16];
 #pragma unroll
@@ -949,71 +668,33 @@ __global__ __launch_bounds__(NT) void bwd_dkv64_kernel(
       bf16x8 s1 = pack_fragment(ds, 8);
 #pragma unroll
       for (int t = 0; t < DTILES; ++t) {
-        union { unsigned u[4]; bf16x8 v8; } ado0, ado1, aq0, aq1;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          reinterpret_cast<__hip_bfloat16*>(&ado0)[e] = dot_lds[(t * 32 + l31) * QT_STRIDE + qrow_off + hhalf * 8 + e];
-          reinterpret_cast<__hip_bfloat16*>(&ado1)[e] = dot_lds[(t * 32 + l31) * QT_STRIDE + qrow_off + 16 + hhalf * 8 + e];
-          reinterpret_cast<__hip_bfloat16*>(&aq0)[e] = qt_lds[(t * 32 + l31) * QT_STRIDE + qrow_off + hhalf * 8 + e];
-          reinterpret_cast<__hip_bfloat16*>(&aq1)[e] = qt_lds[(t * 32 + l31) * QT_STRIDE + qrow_off + 16 + hhalf * 8 + e];
-        }
-        f32x16 accv, acck;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          accv[r] = dv_acc[t][r];
-          acck[r] = dk_acc[t][r];
-        }
-        accv = MFMA32(ado0.v8, p0, accv);
-        accv = MFMA32(ado1.v8, p1, accv);
-        acck = MFMA32(aq0.v8, s0, acck);
-        acck = MFMA32(aq1.v8, s1, acck);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          dv_acc[t][r] = accv[r];
-          dk_acc[t][r] = acck[r];
-        }
+        // A[i = d = t*32 + l31][q = hhalf*8 + e] and the same 16 rows further
+        const int a0 = (t * 32 + l31) * QT_STRIDE + qrow_off + hhalf * 8;
+        mfma2_acc(dv_acc[t], gather8(dot_lds + a0, 1), p0, gather8(dot_lds + a0 + 16, 1), p1);
+        mfma2_acc(dk_acc[t], gather8(qt_lds + a0, 1), s0, gather8(qt_lds + a0 + 16, 1), s1);
       }
     }
   }
 
   if (krow < N) {
-    const int p = krow - prefix;
-    if constexpr (MODE != 1) {
-      if (use_rope && p >= 0) {
-        const float* srow = sin_t + (long)p * HD;
-        const float* crow = cos_t + (long)p * HD;
-#pragma unroll
-        for (int t = 0; t < DTILES / 2; ++t)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int d = t * 32 + c_row(r, hhalf);
-            const float c = crow[d], s = srow[d];
-            const float glo = dk_acc[t][r], ghi = dk_acc[t + DTILES / 2][r];
-            dk_acc[t][r] = glo * c + ghi * s;
-            dk_acc[t + DTILES / 2][r] = ghi * c - glo * s;
-          }
-      }
-    }
-    __hip_bfloat16* dkp = dqkv + ((((long)b * N + krow) * 3 + 1) * H + h) * HD;
-    __hip_bfloat16* dvp = dqkv + ((((long)b * N + krow) * 3 + 2) * H + h) * HD;
-#pragma unroll
-    for (int t = 0; t < DTILES; ++t)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int d = t * 32 + c_row(r, hhalf);
-        if constexpr (MODE != 1)
-          *reinterpret_cast<short*>(dkp + d) = f32_to_bf16(dk_acc[t][r]);
-        if constexpr (MODE != 2)
-          *reinterpret_cast<short*>(dvp + d) = f32_to_bf16(dv_acc[t][r]);
-      }
+    rope_inverse(dk_acc, sin_t, cos_t, krow, c);
+    store_rows_bf16(lay.grad_row(grad, 1, krow), dk_acc, hhalf);
+    store_rows_bf16(lay.grad_row(grad, 2, krow), dv_acc, hhalf);
   }
 }
 
-// preprocess on token-major dO/O: D[b,h,n] = sum_d dO*O
+// ---------------------------------------------------------------------------
+// Backward preprocess: D[b,h,n] = sum_d dO*O (fp32), rows ordered (b, h, n).
+// One wave per 8 rows: 8 lanes per row, 8 bf16 per lane per pass. (The name
+// dates from the token-major-only version; kept so traces stay comparable.)
+// ---------------------------------------------------------------------------
+constexpr int PRE_THREADS = 256;
+constexpr int PRE_ROWS = PRE_THREADS / 64 * 8;  // rows per block and pass
+
+template <class L>
 __global__ void bwd_pre_tm_kernel(const __hip_bfloat16* __restrict__ dout,
                                   const __hip_bfloat16* __restrict__ o,
                                   float* __restrict__ D, int B, int H, int N, int HD) {
-  // rows ordered (b, h, n) in D; data token-major (b, n, h, d)
   const long rows = (long)B * H * N;
   const int lane = threadIdx.x & 63;
   const int wid = threadIdx.x / 64;
@@ -1027,154 +708,180 @@ __global__ void bwd_pre_tm_kernel(const __hip_bfloat16* __restrict__ dout,
       const int n = (int)(row % N);
       const int h = (int)((row / N) % H);
       const int b = (int)(row / ((long)N * H));
-      const long off = (((long)b * N + n) * H + h) * HD;
+      const L lay(b, h, H, N, HD);
+      const __hip_bfloat16* dop = lay.o_row(dout, n);
+      const __hip_bfloat16* op = lay.o_row(o, n);
       for (int i0 = lane8 * 8; i0 < HD; i0 += 64) {
         __hip_bfloat16 a[8], c[8];
-        Vec8<__hip_bfloat16>::load(a, dout + off + i0);
-        Vec8<__hip_bfloat16>::load(c, o + off + i0);
+        Vec8<__hip_bfloat16>::load(a, dop + i0);
+        Vec8<__hip_bfloat16>::load(c, op + i0);
 #pragma unroll
         for (int e = 0; e < 8; ++e)
           acc += bf16_to_f32(*(short*)(a + e)) * bf16_to_f32(*(short*)(c + e));
       }
     }
+    // reduce across the 8 lanes of this row
 #pragma unroll
     for (int off = 4; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
     if (lane8 == 0 && row < rows) D[row] = acc;
   }
 }
 
-}  // namespace fmha_rope
-
 // ---------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------
 
-void launch_fmha_rope_fwd(const __hip_bfloat16* qkv, const float* sin_t,
-                          const float* cos_t, __hip_bfloat16* o, float* lse, int B, int H,
-                          int N, int P, int HD, float scale, hipStream_t stream) {
-  // short sequences (local crops, N <= 64): 128-thread blocks, 64 q rows each
-  const bool small = N <= 64;
-  dim3 grid(B * H, small ? 1 : (N + 127) / 128);
+constexpr size_t LDS_DEFAULT_MAX = 64 * 1024;  // dynamic LDS a launch gets without opting in
+
+// SMEM comes from the kernel's own *Smem traits. OPT_IN raises the kernel's
+// dynamic-LDS limit first (once per kernel).
+template <auto KERNEL, size_t SMEM, bool OPT_IN, class... A>
+static void launch(dim3 grid, int nt, hipStream_t stream, A... args) {
+  static_assert(SMEM <= LDS_DEFAULT_MAX || OPT_IN,
+                "more than 64 KiB of dynamic LDS needs the opt-in launch path");
+  if constexpr (OPT_IN) {
+    static const bool attr_ok =
+        hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, SMEM) == hipSuccess;
+    (void)attr_ok;
+  }
+  hipLaunchKernelGGL(KERNEL, grid, dim3(nt), SMEM, stream, args...);
+}
+
+template <class L, int HD, int NT, bool QLDS, bool PREFETCH, int MINW, int KVB, class... A>
+static void run_fwd(dim3 grid, hipStream_t stream, A... args) {
+  launch<fwd_kernel<L, HD, NT, QLDS, PREFETCH, MINW, KVB>, FwdSmem<HD, NT, QLDS, KVB>::BYTES,
+         QLDS>(grid, NT, stream, args...);
+}
+template <class L, int HD, int NT, int MINW, int KVB, class... A>
+static void run_dq(dim3 grid, hipStream_t stream, A... args) {
+  launch<bwd_dq_kernel<L, HD, NT, MINW, KVB>, DqSmem<HD, KVB>::BYTES, false>(grid, NT, stream,
+                                                                             args...);
+}
+template <class L, int HD, int NT, int SQB, class... A>
+static void run_dkv(dim3 grid, hipStream_t stream, A... args) {
+  launch<bwd_dkv_kernel<L, HD, NT, 1, SQB>, DkvSmem<HD, SQB>::BYTES, false>(grid, NT, stream,
+                                                                            args...);
+}
+
+// short sequences (local crops, N <= 64): 128-thread blocks, 64 q rows each
+static bool small_n(int N) { return N <= 64; }
+static dim3 attn_grid(int B, int H, int N) {
+  return dim3(B * H, small_n(N) ? 1 : (N + 127) / 128);
+}
+
+template <class L>
+void launch_fwd(typename L::Qkv in, const float* sin_t, const float* cos_t,
+                __hip_bfloat16* o, float* lse, int B, int H, int N, int P, int HD,
+                float scale, hipStream_t stream) {
+  const dim3 grid = attn_grid(B, H, N);
   if (HD == 64) {
-    if (small) {
-      size_t shmem = (64 * 72 + 64 * 72) * sizeof(__hip_bfloat16);
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(fmha_rope::fwd_kernel<64, 128>), grid, dim3(128),
-                         shmem, stream, qkv, sin_t, cos_t, o, lse, B, H, N, P, scale);
-    } else {
-      // KVB=64: 128 keys per barrier pair; k_lds [128][72], vt_lds [64][136]
-      size_t shmem = (128 * 72 + 64 * 136) * sizeof(__hip_bfloat16);
-      hipLaunchKernelGGL(
-          HIP_KERNEL_NAME(fmha_rope::fwd_kernel<64, 256, false, true, 1, 64>), grid,
-          dim3(256), shmem, stream, qkv, sin_t, cos_t, o, lse, B, H, N, P, scale);
-    }
+    if (small_n(N))
+      run_fwd<L, 64, 128, false, true, 1, 32>(grid, stream, in, sin_t, cos_t, o, lse, B,
+                                              H, N, P, scale);
+    else  // KVB=64: 128 keys per barrier pair
+      run_fwd<L, 64, 256, false, true, 1, 64>(grid, stream, in, sin_t, cos_t, o, lse, B,
+                                              H, N, P, scale);
   } else if (HD == 128) {
-    size_t shmem = (64 * 136 + 128 * 72) * sizeof(__hip_bfloat16);
-    if (small) {
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(fmha_rope::fwd_kernel<128, 128>), grid, dim3(128),
-                         shmem, stream, qkv, sin_t, cos_t, o, lse, B, H, N, P, scale);
-    } else {
-      // QLDS + no-prefetch: 2 waves/SIMD (the register variant runs at 1)
-      auto* kfn = reinterpret_cast<const void*>(
-          HIP_KERNEL_NAME(fmha_rope::fwd_kernel<128, 256, true, false, 2>));
-      static bool attr_ok = [kfn] {
-        return hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   160 * 1024) == hipSuccess;
-      }();
-      (void)attr_ok;
-      size_t shmem_q = shmem + (size_t)(256 / 64) * (128 / 16) * 64 * 8 *
-                                   sizeof(__hip_bfloat16);
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(fmha_rope::fwd_kernel<128, 256, true, false, 2>),
-                         grid, dim3(256), shmem_q, stream, qkv, sin_t, cos_t, o, lse, B,
-                         H, N, P, scale);
-    }
+    if (small_n(N))
+      run_fwd<L, 128, 128, false, true, 1, 32>(grid, stream, in, sin_t, cos_t, o, lse, B,
+                                               H, N, P, scale);
+    else  // QLDS + no-prefetch: 2 waves/SIMD (the register variant runs at 1)
+      run_fwd<L, 128, 256, true, false, 2, 32>(grid, stream, in, sin_t, cos_t, o, lse, B,
+                                               H, N, P, scale);
   }
 }
 
-void launch_fmha_rope_bwd_pre(const __hip_bfloat16* dout, const __hip_bfloat16* o,
-                              float* D, int B, int H, int N, int HD, hipStream_t stream) {
-  long rows = (long)B * H * N;
-  int grid = (int)min((rows + 31) / 32, (long)4096);
-  hipLaunchKernelGGL(fmha_rope::bwd_pre_tm_kernel, dim3(grid), dim3(256), 0, stream, dout,
-                     o, D, B, H, N, HD);
+template <class L>
+void launch_bwd_pre(const __hip_bfloat16* dout, const __hip_bfloat16* o, float* D, int B,
+                    int H, int N, int HD, hipStream_t stream) {
+  const long rows = (long)B * H * N;
+  const int grid = (int)min((rows + PRE_ROWS - 1) / PRE_ROWS, (long)4096);
+  hipLaunchKernelGGL(bwd_pre_tm_kernel<L>, dim3(grid), dim3(PRE_THREADS), 0, stream, dout, o,
+                     D, B, H, N, HD);
 }
 
-void launch_fmha_rope_bwd_dq(const __hip_bfloat16* qkv, const __hip_bfloat16* dout,
-                             const float* sin_t, const float* cos_t, const float* lse,
-                             const float* D, __hip_bfloat16* dqkv, int B, int H, int N,
-                             int P, int HD, float scale, hipStream_t stream) {
-  const bool small = N <= 64;
-  dim3 grid(B * H, small ? 1 : (N + 127) / 128);
+template <class L>
+void launch_bwd_dq(typename L::Qkv in, const __hip_bfloat16* dout, const float* sin_t,
+                   const float* cos_t, const float* lse, const float* D,
+                   typename L::DQkv grad, int B, int H, int N, int P, int HD, float scale,
+                   hipStream_t stream) {
+  const dim3 grid = attn_grid(B, H, N);
   if (HD == 64) {
-    size_t shmem = (2 * 64 * 72 + 64 * 72) * sizeof(__hip_bfloat16);
-    if (small)
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(fmha_rope::bwd_dq_kernel<64, 128>), grid,
-                         dim3(128), shmem, stream, qkv, dout, sin_t, cos_t, lse, D, dqkv,
-                         B, H, N, P, scale);
-    else {
-      // KVB=64: 128 keys per barrier pair (k_lds+v_lds [128][72], kt [64][136])
-      size_t shmem64 = (2 * 128 * 72 + 64 * 136) * sizeof(__hip_bfloat16);
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(fmha_rope::bwd_dq_kernel<64, 256, 2, 64>), grid,
-                         dim3(256), shmem64, stream, qkv, dout, sin_t, cos_t, lse, D,
-                         dqkv, B, H, N, P, scale);
-    }
+    if (small_n(N))
+      run_dq<L, 64, 128, 1, 32>(grid, stream, in, dout, sin_t, cos_t, lse, D, grad, B, H,
+                                N, P, scale);
+    else  // KVB=64: 128 keys per barrier pair
+      run_dq<L, 64, 256, 2, 64>(grid, stream, in, dout, sin_t, cos_t, lse, D, grad, B, H,
+                                N, P, scale);
   } else if (HD == 128) {
-    size_t shmem = (2 * 64 * 136 + 128 * 72) * sizeof(__hip_bfloat16);
-    if (small)
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(fmha_rope::bwd_dq_kernel<128, 128>), grid,
-                         dim3(128), shmem, stream, qkv, dout, sin_t, cos_t, lse, D, dqkv,
-                         B, H, N, P, scale);
-    else
-      // MINW=2 packs to 256 regs (20 B/lane cold scratch) for 2 waves/SIMD
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(fmha_rope::bwd_dq_kernel<128, 256, 2>), grid,
-                         dim3(256), shmem, stream, qkv, dout, sin_t, cos_t, lse, D, dqkv,
-                         B, H, N, P, scale);
+    if (small_n(N))
+      run_dq<L, 128, 128, 1, 32>(grid, stream, in, dout, sin_t, cos_t, lse, D, grad, B,
+                                 H, N, P, scale);
+    else  // MINW=2 packs to 256 regs (20 B/lane cold scratch) for 2 waves/SIMD
+      run_dq<L, 128, 256, 2, 32>(grid, stream, in, dout, sin_t, cos_t, lse, D, grad, B,
+                                 H, N, P, scale);
   }
 }
 
-void launch_fmha_rope_bwd_dkv(const __hip_bfloat16* qkv, const __hip_bfloat16* dout,
-                              const float* sin_t, const float* cos_t, const float* lse,
-                              const float* D, __hip_bfloat16* dqkv, int B, int H, int N,
-                              int P, int HD, float scale, hipStream_t stream) {
-  const bool small = N <= 64;
-  // Gated 64-row super-tile variant (see bwd_dkv64_kernel); only useful when
-  // there is more than one 32-row q-tile. getenv per launch is ~ns vs the
-  // 100 us kernel and keeps the flag flippable from tests. Flip
-  // DKV64_DEFAULT to 1 in round 2 after hardware validation.
-  constexpr bool DKV64_DEFAULT = false;
-  const char* dkv64 = getenv("DINOV3_FMHA_DKV64");
-  const bool dkv64_on = dkv64 ? (dkv64[0] == '1') : DKV64_DEFAULT;
-  const bool use64 = !small && dkv64_on;
-  dim3 grid(B * H, small ? 1 : (N + 127) / 128);
+template <class L>
+void launch_bwd_dkv(typename L::Qkv in, const __hip_bfloat16* dout, const float* sin_t,
+                    const float* cos_t, const float* lse, const float* D,
+                    typename L::DQkv grad, int B, int H, int N, int P, int HD, float scale,
+                    hipStream_t stream) {
+  const dim3 grid = attn_grid(B, H, N);
+  // DINOV3_FMHA_DKV64=1 stages 64 q rows per barrier pair where there is more
+  // than one 32-row q tile (measured neutral twice, kept for reproduction).
+  // getenv per launch is ~ns against the 100 us kernel and keeps the flag
+  // flippable from tests.
+  // Packed layout only, as before the layouts shared these launchers.
+  constexpr int SQB_OPT = L::DKV64_OPTION ? 64 : 32;
+  const char* dkv64 = L::DKV64_OPTION ? getenv("DINOV3_FMHA_DKV64") : nullptr;
+  const bool use64 = !small_n(N) && dkv64 && dkv64[0] == '1';
   if (HD == 64) {
-    size_t shmem = 2 * 64 * 72 * sizeof(__hip_bfloat16) + 128 * sizeof(float);
-    if (small)
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(fmha_rope::bwd_dkv_kernel<64, 128>), grid,
-                         dim3(128), shmem, stream, qkv, dout, sin_t, cos_t, lse, D, dqkv,
-                         B, H, N, P, scale);
+    if (small_n(N))
+      run_dkv<L, 64, 128, 32>(grid, stream, in, dout, sin_t, cos_t, lse, D, grad, B, H, N, P,
+                              scale);
     else if (use64)
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(fmha_rope::bwd_dkv64_kernel<64, 256>), grid,
-                         dim3(256), shmem, stream, qkv, dout, sin_t, cos_t, lse, D, dqkv,
-                         B, H, N, P, scale);
+      run_dkv<L, 64, 256, SQB_OPT>(grid, stream, in, dout, sin_t, cos_t, lse, D, grad, B, H, N, P,
+                              scale);
     else
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(fmha_rope::bwd_dkv_kernel<64, 256>), grid,
-                         dim3(256), shmem, stream, qkv, dout, sin_t, cos_t, lse, D, dqkv,
-                         B, H, N, P, scale);
+      run_dkv<L, 64, 256, 32>(grid, stream, in, dout, sin_t, cos_t, lse, D, grad, B, H, N, P,
+                              scale);
   } else if (HD == 128) {
-    size_t shmem = 2 * 128 * 72 * sizeof(__hip_bfloat16) + 128 * sizeof(float);
-    if (small)
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(fmha_rope::bwd_dkv_kernel<128, 128>), grid,
-                         dim3(128), shmem, stream, qkv, dout, sin_t, cos_t, lse, D, dqkv,
-                         B, H, N, P, scale);
+    if (small_n(N))
+      run_dkv<L, 128, 128, 32>(grid, stream, in, dout, sin_t, cos_t, lse, D, grad, B, H, N,
+                               P, scale);
     else if (use64)
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(fmha_rope::bwd_dkv64_kernel<128, 256>), grid,
-                         dim3(256), shmem, stream, qkv, dout, sin_t, cos_t, lse, D, dqkv,
-                         B, H, N, P, scale);
+      run_dkv<L, 128, 256, SQB_OPT>(grid, stream, in, dout, sin_t, cos_t, lse, D, grad, B, H, N,
+                               P, scale);
     else
-      // combined kernel (occupancy 1 from the 366-reg dual accumulators):
-      // the MODE=1/2 dV/dK split reaches 2 waves/SIMD but re-streams Q/dO
-      // and measured ~5% SLOWER end to end (r2_gpu15) — not used
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(fmha_rope::bwd_dkv_kernel<128, 256>), grid,
-                         dim3(256), shmem, stream, qkv, dout, sin_t, cos_t, lse, D, dqkv,
-                         B, H, N, P, scale);
+      // occupancy 1 (366 regs with both accumulator sets). A dV-only / dK-only
+      // split reached 2 waves/SIMD but measured about 5% slower end to end
+      // (it re-streams Q/dO), so it was removed.
+      run_dkv<L, 128, 256, 32>(grid, stream, in, dout, sin_t, cos_t, lse, D, grad, B, H, N,
+                               P, scale);
   }
+}
+
+#define INSTANTIATE_LAUNCHERS(L)                                                            \
+  template void launch_fwd<L>(L::Qkv, const float*, const float*, __hip_bfloat16*, float*,  \
+                              int, int, int, int, int, float, hipStream_t);                 \
+  template void launch_bwd_pre<L>(const __hip_bfloat16*, const __hip_bfloat16*, float*, int, \
+                                  int, int, int, hipStream_t);                              \
+  template void launch_bwd_dq<L>(L::Qkv, const __hip_bfloat16*, const float*, const float*, \
+                                 const float*, const float*, L::DQkv, int, int, int, int,   \
+                                 int, float, hipStream_t);                                  \
+  template void launch_bwd_dkv<L>(L::Qkv, const __hip_bfloat16*, const float*, const float*, \
+                                  const float*, const float*, L::DQkv, int, int, int, int,  \
+                                  int, float, hipStream_t);
+INSTANTIATE_LAUNCHERS(PackedLayout)
+INSTANTIATE_LAUNCHERS(PlainLayout)
+#undef INSTANTIATE_LAUNCHERS
+
+}  // namespace fmha_rope
+
+void launch_probe_mfma(const __hip_bfloat16* A, const __hip_bfloat16* B, float* C,
+                       hipStream_t stream) {
+  hipLaunchKernelGGL(fmha_rope::probe_mfma_kernel, dim3(1), dim3(64), 0, stream, A, B, C);
 }

@@ -57,10 +57,10 @@
 // conflicts. The staging stores are ds_write_b128 of 8 consecutive lanes to
 // 128 contiguous bytes of one row: 32 distinct banks.
 
-#include "common.h"
+#include "mfma.h"
 
-typedef __attribute__((ext_vector_type(8))) __bf16 knn_bf16x8;
-typedef __attribute__((ext_vector_type(16))) float knn_f32x16;
+typedef bf16x8 knn_bf16x8;
+typedef f32x16 knn_f32x16;
 
 #define KNN_TQ 32        // queries per block (one MFMA tile wide)
 #define KNN_BN 128       // bank rows per staged tile, 32 per wave
@@ -87,9 +87,6 @@ DEV_INLINE float key_value(key_t key) {
 }
 
 DEV_INLINE unsigned key_row(key_t key) { return 0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull); }
-
-// Bank rows held by accumulator register r of lane half h (32x32 MFMA C map).
-DEV_INLINE int c_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
 // KCAP: largest k of the instantiation. ws != nullptr: write the block's
 // sorted keys (0 past the end of a short list) to ws[split, query, k];

@@ -8,20 +8,14 @@
 // 32 rows x 128 cols = 2x4 accumulators of v_mfma_f32_32x32x16_bf16), LDS
 // double-purpose staging of the A rows and the W slice per K-step of 32.
 
-#include "common.h"
+#include "mfma.h"
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_pe;
-typedef __attribute__((ext_vector_type(16))) float f32x16_pe;
+typedef bf16x8 bf16x8_pe;
+typedef f32x16 f32x16_pe;
 
 #define PE_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0)
 
 namespace patch_embed {
-
-DEV_INLINE bf16x8_pe load8(const __hip_bfloat16* p) {
-  return *reinterpret_cast<const bf16x8_pe*>(p);
-}
-
-DEV_INLINE int c_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
 // x: [B, C, H, W] bf16 ; w: [D, K] bf16 (K = C*P*P) ; bias: [D] bf16
 // out: [B*np, D] bf16 with np = (H/P)*(W/P). P is the template patch size.

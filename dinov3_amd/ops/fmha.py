@@ -2,9 +2,11 @@
 
 DINOv3 sequence lengths are tiny by LLM standards (37 local / 197-201 global /
 up to 2309 high-res) at large batch x heads; head_dim 64 (ViT-S..g) or 128
-(ViT-7B). The MI355X kernel (csrc/fmha.hip) therefore tiles over (batch*heads)
-across the 256 CUs with whole-K/V-in-LDS flash-style blocks on
-v_mfma_f32_16x16x32_bf16, fp32 softmax, bf16 I/O.
+(ViT-7B). The MI355X kernels (csrc/fmha_rope.hip, plain [B, H, N, hd] layout,
+no RoPE) therefore tile over (batch*heads, 128-row q blocks) across the 256
+CUs, stream K/V through LDS in 64- or 128-key tiles on
+v_mfma_f32_32x32x16_bf16, fp32 online softmax, bf16 I/O. They are the same
+kernels the model runs on the packed qkv buffer (ops/flat_attention.py).
 
 Forward returns the row log-sum-exp for the backward recompute pass
 (flash-attention-2 style backward).

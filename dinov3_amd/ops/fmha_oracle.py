@@ -1,5 +1,5 @@
 """fp64 oracle, elementwise rounding bounds and test-case generators for the
-fused RoPE + attention kernels (csrc/fmha_rope.hip, csrc/fmha.hip).
+fused RoPE + attention kernels (csrc/fmha_rope.hip).
 
 Pure torch on the CPU; nothing here touches the HIP extension. Everything works
 per crop group on ``qkv [B, N, 3, H, hd]`` with ``sin``/``cos`` tables of shape
@@ -24,12 +24,9 @@ of the absolute values. Every term is doubled because the summation order
 inside an MFMA is undocumented (tests/test_fp8_gpu.py
 ``test_gemm_random_within_rounding_bound`` does the same).
 
-csrc/fmha.hip (the older q/k/v entry points ``fmha_fwd``/``fmha_bwd``) rounds at
-exactly the same points as csrc/fmha_rope.hip without RoPE — bf16 P before PV,
-bf16 O, D from the bf16 O, bf16 dS and P before the gradient GEMMs, fp32
-everywhere else — and only tiles the keys in 32s instead of 64s/128s, which no
-term depends on. It therefore needs no term of its own: use the same oracle and
-bounds with ``sin = cos = None``.
+The q/k/v entry points ``fmha_fwd``/``fmha_bwd`` run the same kernels through
+their plain ``[B, H, N, hd]`` memory layout, without RoPE: use the same oracle
+and bounds with ``sin = cos = None``.
 """
 
 from __future__ import annotations

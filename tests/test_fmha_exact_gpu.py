@@ -22,10 +22,10 @@ DEV = "cuda:0"
 B, H = 2, 3   # values differ per (b, h) and H is no power of two: stride mix-ups show
 SHAPE_IDS = [f"N{n}-hd{hd}-p{p}-{'rope' if r else 'norope'}" for n, hd, p, r in fo.EDGE_SHAPES]
 SHAPES = list(range(len(fo.EDGE_SHAPES)))
-# (shape, dkv64): the gated 64-row dK/dV kernel only exists on the N > 64 path
+# (shape, dkv64): the gated 64-row dK/dV staging only exists on the N > 64 path
 BWD_CASES = [(i, False) for i in SHAPES] + [(i, True) for i in SHAPES if fo.EDGE_SHAPES[i][0] > 64]
 BWD_IDS = [SHAPE_IDS[i] + ("-dkv64" if d else "") for i, d in BWD_CASES]
-# the older q/k/v entry points (csrc/fmha.hip): (N, hd), no RoPE
+# the q/k/v [B, H, N, hd] entry points (the kernels' plain layout): (N, hd), no RoPE
 QKV_SHAPES = [(33, 64), (129, 64), (197, 128)]
 
 
@@ -205,7 +205,7 @@ def test_bwd_multi_group_flat_buffer(monkeypatch):
 
 
 # ---------------------------------------------------------------------------
-# the older q/k/v entry points: fmha_fwd, fmha_bwd, ops.fmha  (csrc/fmha.hip)
+# the q/k/v entry points: fmha_fwd, fmha_bwd, ops.fmha  (plain-layout kernels)
 # ---------------------------------------------------------------------------
 
 def _split_qkv(case):
@@ -261,3 +261,28 @@ def test_qkv_entry_points_onehot(N, hd):
     assert torch.equal(_bits(_tm(out)), _bits(want_o))
     assert torch.equal(_bits(_tm(v.grad)), _bits(want_dv))
     assert torch.equal(q.grad.float().cpu(), torch.zeros(q.shape)) and torch.equal(k.grad.float().cpu(), torch.zeros(k.shape))
+
+
+@pytest.mark.parametrize("N,hd", QKV_SHAPES)
+def test_plain_and_packed_entry_points_bit_identical(N, hd):
+    """There is one kernel per pass: the q/k/v entry points and the packed-qkv
+    ones differ in addressing only, so their results agree bit for bit.
+    (33, 64): small-N path, partial tile; (129, 64): two q blocks with a
+    one-row tail, 128-key staging; (197, 128): Q-in-LDS forward, MINW-2 dq."""
+    from dinov3_amd.ops import hip_ops
+
+    case = _fewbit_ref(N, hd, 0, False, 1.0)[0]
+    qkv = case.qkv.to(DEV)
+    do_tm = case.dO.to(DEV)
+    e = torch.empty(0, device=DEV)
+    o_p, lse_p = hip_ops().fmha_rope_fwd(qkv, e, e, 0)
+    g = hip_ops().fmha_rope_bwd(do_tm, qkv, o_p, lse_p, e, e, 0)
+
+    q, k, v = _split_qkv(case)
+    o, lse = hip_ops().fmha_fwd(q, k, v)
+    gq, gk, gv = hip_ops().fmha_bwd(do_tm.permute(0, 2, 1, 3).contiguous(), q, k, v, o, lse)
+
+    assert torch.equal(_bits(o.permute(0, 2, 1, 3)), _bits(o_p))
+    assert torch.equal(lse.view(torch.int32), lse_p.view(torch.int32))
+    for w, (name, got) in enumerate((("dq", gq), ("dk", gk), ("dv", gv))):
+        assert torch.equal(_bits(got.permute(0, 2, 1, 3)), _bits(g[:, :, w])), name

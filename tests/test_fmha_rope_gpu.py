@@ -116,11 +116,44 @@ def test_flat_multi_group():
         assert err < 0.03, f"group err {err}"
 
 
+def test_bindings_refuse_bad_arguments():
+    """The wrappers check every tensor the kernels dereference before any launch."""
+    from dinov3_amd.ops import hip_ops
+
+    ops = hip_ops()
+    torch.manual_seed(4)
+    B, N, H, hd = 1, 8, 1, 64
+    qkv = torch.randn(B, N, 3, H, hd, device=DEV).bfloat16()
+    angles = torch.rand(N, hd, device=DEV)
+    sin, cos = angles.sin(), angles.cos()
+    o, lse = ops.fmha_rope_fwd(qkv, sin, cos, 0)
+    dout = torch.randn_like(o)
+    none = torch.empty(0, device=DEV)
+
+    def strided(x):  # same shape and values, every other element of a wider buffer
+        wide = torch.empty(*x.shape[:-1], 2 * x.shape[-1], dtype=x.dtype, device=DEV)
+        view = wide[..., ::2]
+        view.copy_(x)
+        assert not view.is_contiguous()
+        return view
+
+    ops.fmha_rope_bwd_out(dout, qkv, o, lse, sin, cos, 0, torch.empty_like(qkv))  # accepted
+    for bad in (dict(out_dqkv=strided(qkv)), dict(qkv=strided(qkv)), dict(lse=lse.half())):
+        a = dict(qkv=qkv, lse=lse, out_dqkv=torch.empty_like(qkv))
+        a.update(bad)
+        with pytest.raises(RuntimeError, match="fmha: "):
+            ops.fmha_rope_bwd_out(dout, a["qkv"], o, a["lse"], sin, cos, 0, a["out_dqkv"])
+
+    with pytest.raises(RuntimeError, match="cos_t must match sin_t"):
+        ops.fmha_rope_fwd_out(qkv, sin, cos[:-1], 0, none)
+    with pytest.raises(RuntimeError, match="fmha: out_o"):
+        ops.fmha_rope_fwd_out(qkv, sin, cos, 0, torch.empty(B, N, H, hd + 1, dtype=qkv.dtype, device=DEV))
+
+
 @pytest.mark.parametrize("N,hd,prefix", [(197, 64, 1), (197, 128, 1), (300, 64, 2), (128, 64, 0)])
 def test_dkv64_variant(N, hd, prefix, monkeypatch):
-    """Gated 64-row super-tile dkv kernel vs the fp32 reference (the round-1
-    attempt NaN'd from a 32-row LDS stride; this variant fixes the staging
-    layout — flip DINOV3_FMHA_DKV64 on by default once this passes)."""
+    """Gated 64-row dkv staging (DINOV3_FMHA_DKV64=1) vs the fp32 reference
+    (the round-1 attempt NaN'd from a 32-row LDS stride)."""
     monkeypatch.setenv("DINOV3_FMHA_DKV64", "1")
     from dinov3_amd.ops.flat_attention import flat_multi_fmha
 
