@@ -847,6 +847,11 @@ static RopeTables rope_tables(const AttnDims& d, const torch::Tensor& sin_t,
   return {sin_t.data_ptr<float>(), cos_t.data_ptr<float>(), P};
 }
 
+// single-pass backward where one workgroup holds the sequence, unless switched off
+static bool use_fused_bwd(const AttnDims& d) {
+  return fmha_rope::fused_bwd_supported(d.N, d.HD) && fmha_rope::fused_bwd_enabled();
+}
+
 std::vector<torch::Tensor> fmha_fwd(torch::Tensor q, torch::Tensor k, torch::Tensor v) {
   using L = fmha_rope::PlainLayout;
   const AttnDims d = plain_dims(q, k, v);
@@ -863,13 +868,19 @@ std::vector<torch::Tensor> fmha_bwd(torch::Tensor dout, torch::Tensor q, torch::
   using L = fmha_rope::PlainLayout;
   const AttnDims d = plain_dims(q, k, v);
   check_bwd_inputs(d, dout, o, lse);
-  auto D = torch::empty({d.B, d.H, d.N}, q.options().dtype(torch::kFloat));
   auto dq = torch::empty_like(q);
   auto dk = torch::empty_like(k);
   auto dv = torch::empty_like(v);
   const L::Qkv in{bf16_in(q), bf16_in(k), bf16_in(v)};
   const L::DQkv grad{bf16_out(dq), bf16_out(dk), bf16_out(dv)};
   auto stream = current_stream();
+  if (use_fused_bwd(d)) {
+    fmha_rope::launch_bwd_fused<L>(in, bf16_in(dout), bf16_in(o), nullptr, nullptr,
+                                   lse.data_ptr<float>(), grad, d.B, d.H, d.N, d.N, d.HD,
+                                   d.scale(), stream);
+    return {dq, dk, dv};
+  }
+  auto D = torch::empty({d.B, d.H, d.N}, q.options().dtype(torch::kFloat));
   fmha_rope::launch_bwd_pre<L>(bf16_in(dout), bf16_in(o), D.data_ptr<float>(), d.B, d.H, d.N,
                                d.HD, stream);
   fmha_rope::launch_bwd_dq<L>(in, bf16_in(dout), nullptr, nullptr, lse.data_ptr<float>(),
@@ -929,13 +940,19 @@ torch::Tensor fmha_rope_bwd_out(torch::Tensor dout, torch::Tensor qkv, torch::Te
   const AttnDims d = packed_dims(qkv);
   check_bwd_inputs(d, dout, o, lse);
   const RopeTables rope = rope_tables(d, sin_t, cos_t, prefix);
-  auto D = torch::empty({d.B, d.H, d.N}, qkv.options().dtype(torch::kFloat));
   torch::Tensor dqkv = out_dqkv.defined() && out_dqkv.numel() > 0 ? out_dqkv
                                                                   : torch::empty_like(qkv);
   check_attn(dqkv, at::kBFloat16, 3 * d.numel(), "out_dqkv");
   const L::Qkv in{bf16_in(qkv)};
   const L::DQkv grad{bf16_out(dqkv)};
   auto stream = current_stream();
+  if (use_fused_bwd(d)) {
+    fmha_rope::launch_bwd_fused<L>(in, bf16_in(dout), bf16_in(o), rope.sin, rope.cos,
+                                   lse.data_ptr<float>(), grad, d.B, d.H, d.N, rope.P, d.HD,
+                                   d.scale(), stream);
+    return dqkv;
+  }
+  auto D = torch::empty({d.B, d.H, d.N}, qkv.options().dtype(torch::kFloat));
   fmha_rope::launch_bwd_pre<L>(bf16_in(dout), bf16_in(o), D.data_ptr<float>(), d.B, d.H, d.N,
                                d.HD, stream);
   fmha_rope::launch_bwd_dq<L>(in, bf16_in(dout), rope.sin, rope.cos, lse.data_ptr<float>(),
@@ -1548,6 +1565,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   });
   mod.def("fmha_rope_bwd_out", &fmha_rope_bwd_out);
   mod.def("fmha_bwd", &fmha_bwd);
+  mod.def("fmha_fused_bwd_supported", [](int64_t N, int64_t hd) {
+    return fmha_rope::fused_bwd_supported((int)N, (int)hd);
+  });
   mod.def("multi_tensor_ema", &multi_tensor_ema);
   mod.def("multi_tensor_ema_planned", &multi_tensor_ema_planned);
   mod.def("multi_tensor_adamw_planned", &multi_tensor_adamw_planned);

@@ -88,6 +88,18 @@ void launch_bwd_dkv(typename L::Qkv in, const __hip_bfloat16* dout, const float*
                     typename L::DQkv grad, int B, int H, int N, int P, int HD, float scale,
                     hipStream_t stream);
 
+// Single-pass backward (pre + dq + dkv in one launch, D computed inside from
+// dO and o) for the shapes fused_bwd_supported(N, HD) names; every other shape
+// takes the three launches above. fused_bwd_enabled() is false while
+// DINOV3_FMHA_FUSED_BWD=0 is set.
+bool fused_bwd_supported(int N, int HD);
+bool fused_bwd_enabled();
+template <class L>
+void launch_bwd_fused(typename L::Qkv in, const __hip_bfloat16* dout, const __hip_bfloat16* o,
+                      const float* sin_t, const float* cos_t, const float* lse,
+                      typename L::DQkv grad, int B, int H, int N, int P, int HD, float scale,
+                      hipStream_t stream);
+
 }  // namespace fmha_rope
 
 void launch_probe_mfma(const __hip_bfloat16* A, const __hip_bfloat16* B, float* C,

@@ -22,10 +22,13 @@
 //   tile's global loads are issued before the compute phase.
 // - backward recomputes P from the saved logsumexp. Three kernels: preprocess
 //   D = rowsum(dO*O); dQ (loop over k tiles); dK/dV (loop over q tiles).
+//   Where one workgroup holds the whole sequence (hd 64, N <= 256) a single
+//   kernel does all three (bwd_fused_kernel): S, P, dP and dS once per tile.
 
 #include "fmha_rope.h"
 #include "mfma.h"
 #include <cstdlib>
+#include <stdexcept>
 
 namespace fmha_rope {
 
@@ -684,6 +687,345 @@ __global__ __launch_bounds__(NT, MINW) void bwd_dkv_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// Backward in one pass, for sequences one workgroup holds (N <= 32 * NT/64):
+// one workgroup per (b, h), wave w owns keys 32w .. 32w+31 as in dkv (rope'd K
+// and V fragments, dK^T / dV^T accumulators in registers) and the workgroup
+// walks the 32-row q slices. Per slice:
+//   stage   rope'd Q and dO, each row-major and transposed, lse, and
+//           D[q] = sum_d dO*O reduced over the 8 lanes that load the row
+//   wave    S = Q @ K^T, dP = dO @ V^T, P, dS once; dV^T += dO^T @ P and
+//           dK^T += Q^T @ dS as in dkv. dS (bf16, the bits dK consumes) is
+//           transposed through the wave's own LDS slot, then the fp32 partial
+//           dQ^T[d, q] = K^T[d, own keys] @ dS^T replaces it there
+//   all     add the slots of the waves that hold keys in wave order, inverse
+//           rope, store the slice's dQ rows
+// Waves whose keys lie wholly past N only stage and reduce. No atomics: the
+// result is a function of the inputs alone.
+// ---------------------------------------------------------------------------
+template <int HD, int NT>
+struct FusedBwdSmem {  // q | dO | Q^T | dO^T || lse, D | per-wave dQ slots
+  static constexpr int QB = 32;               // q rows per slice
+  static constexpr int NW = NT / 64;          // waves = 32-key tiles
+  static constexpr int MAX_N = NW * 32;
+  static constexpr int ROW_STRIDE = HD + 8;   // row-major q / dO (bf16 elements)
+  static constexpr int T_STRIDE = QB + 8;     // Q^T / dO^T / dS^T rows
+  static constexpr int SLOT_STRIDE = HD + 4;  // fp32 elements per q row of a slot
+  static constexpr int DO_OFF = QB * ROW_STRIDE;
+  static constexpr int QT_OFF = 2 * QB * ROW_STRIDE;
+  static constexpr int DOT_OFF = QT_OFF + HD * T_STRIDE;
+  static constexpr int STAT_OFF = DOT_OFF + HD * T_STRIDE;  // end of the bf16 part
+  static constexpr int SLOT_FLOATS = QB * SLOT_STRIDE;
+  static constexpr size_t SLOT_BYTE_OFF = STAT_OFF * sizeof(__hip_bfloat16) + 2 * QB * sizeof(float);
+  static constexpr size_t BYTES = SLOT_BYTE_OFF + (size_t)NW * SLOT_FLOATS * sizeof(float);
+  static_assert(SLOT_BYTE_OFF % 16 == 0 && (ROW_STRIDE * 2) % 16 == 0 && (T_STRIDE * 2) % 16 == 0 &&
+                    (SLOT_STRIDE * 4) % 16 == 0,
+                "16-byte LDS accesses need 16-byte aligned rows");
+  // a slot also serves its own wave as bf16 transposition scratch: [32 keys][ROW_STRIDE]
+  // for K before the loop, [QB][T_STRIDE] for dS^T before the slice's partial is written
+  static_assert(32 * ROW_STRIDE * sizeof(__hip_bfloat16) <= SLOT_FLOATS * sizeof(float) &&
+                QB * T_STRIDE * sizeof(__hip_bfloat16) <= SLOT_FLOATS * sizeof(float));
+  static_assert(BYTES <= 160 * 1024, "one workgroup's LDS on gfx950");
+};
+
+// MINW = 2: 512 threads are two waves per SIMD already; the 128-thread form
+// would otherwise take 350 registers and halve the workgroups per CU
+template <class L, int HD, int NT>
+__global__ __launch_bounds__(NT, 2) void bwd_fused_kernel(
+    typename L::Qkv in, const __hip_bfloat16* __restrict__ dout,
+    const __hip_bfloat16* __restrict__ o, const float* __restrict__ sin_t,
+    const float* __restrict__ cos_t, const float* __restrict__ lse, typename L::DQkv grad,
+    int B, int H, int N, int P, float scale) {
+  using Smem = FusedBwdSmem<HD, NT>;
+  static_assert(HD == 64, "the reduction's thread map is written for hd 64");
+  constexpr int KSLICES = HD / 16;
+  constexpr int DTILES = HD / 32;
+  constexpr int QB = Smem::QB;
+  constexpr int ROW_STRIDE = Smem::ROW_STRIDE;
+  constexpr int T_STRIDE = Smem::T_STRIDE;
+  constexpr int SLOT_STRIDE = Smem::SLOT_STRIDE;
+  constexpr int HALF = HD / 2;
+
+  const BlockCtx c = block_ctx(H, N, P, sin_t);
+  const L lay(c.b, c.h, H, N, HD);
+  const int hhalf = c.hhalf, l31 = c.l31;
+  const int k0 = c.wave * 32;
+  const bool wave_active = k0 < N;
+  const int n_active = (N + 31) / 32;  // waves that hold keys
+
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  __hip_bfloat16* q_lds = reinterpret_cast<__hip_bfloat16*>(smem_raw);
+  __hip_bfloat16* do_lds = q_lds + Smem::DO_OFF;
+  __hip_bfloat16* qt_lds = q_lds + Smem::QT_OFF;
+  __hip_bfloat16* dot_lds = q_lds + Smem::DOT_OFF;
+  float* lse_lds = reinterpret_cast<float*>(q_lds + Smem::STAT_OFF);
+  float* d_lds = lse_lds + QB;
+  float* slots = reinterpret_cast<float*>(smem_raw + Smem::SLOT_BYTE_OFF);
+  float* my_slot = slots + c.wave * Smem::SLOT_FLOATS;
+  __hip_bfloat16* ds_lds = reinterpret_cast<__hip_bfloat16*>(my_slot);
+
+  // wave-resident K (rope'd) and V: B fragments [d, key = l31]
+  const int krow = k0 + l31;
+  const int safe = krow < N ? krow : (N - 1);
+  bf16x8 kf[KSLICES], vf[KSLICES];
+#pragma unroll
+  for (int s = 0; s < KSLICES; ++s) {
+    kf[s] = load8(lay.at(in, safe, 1, s * 16 + hhalf * 8));
+    vf[s] = load8(lay.at(in, safe, 2, s * 16 + hhalf * 8));
+  }
+  rope_fragments(kf, sin_t, cos_t, safe, c);
+  // the same K as A fragments K^T[d = t*32 + l31][key = u*16 + hhalf*8 + e] of
+  // the dQ product: transposed once through the wave's own slot
+  bf16x8 ktf[DTILES][2];
+  {
+    __hip_bfloat16* scr = reinterpret_cast<__hip_bfloat16*>(my_slot);
+#pragma unroll
+    for (int s = 0; s < KSLICES; ++s)
+      *reinterpret_cast<bf16x8*>(&scr[l31 * ROW_STRIDE + s * 16 + hhalf * 8]) = kf[s];
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+    for (int t = 0; t < DTILES; ++t)
+#pragma unroll
+      for (int u = 0; u < 2; ++u)
+        ktf[t][u] = gather8(scr + (u * 16 + hhalf * 8) * ROW_STRIDE + t * 32 + l31, ROW_STRIDE);
+  }
+
+  float dk_acc[DTILES][16], dv_acc[DTILES][16];
+#pragma unroll
+  for (int t = 0; t < DTILES; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      dk_acc[t][r] = 0.f;
+      dv_acc[t][r] = 0.f;
+    }
+
+  // staging of one 32-row slice: Q as (lo, hi) pair chunks for the rope, dO
+  // and O as 8-element chunks, 8 consecutive lanes per row
+  constexpr int PAIRS_PER_ROW = HALF / 8;
+  constexpr int PER_ROW = HD / 8;
+  constexpr int QK_ITEMS = QB * PAIRS_PER_ROW;
+  constexpr int DO_ITEMS = QB * PER_ROW;
+  constexpr int QK_IPT = (QK_ITEMS + NT - 1) / NT;
+  constexpr int DO_IPT = (DO_ITEMS + NT - 1) / NT;
+  // dO / O chunks start at thread DO_T0: behind the Q chunks where the block has
+  // threads for both, so that no wave stages both
+  constexpr int DO_T0 = (NT >= QK_ITEMS + DO_ITEMS) ? NT - DO_ITEMS : 0;
+  static_assert(PER_ROW == 8 && NT % 8 == 0 && DO_T0 % 8 == 0,
+                "D is reduced over 8 consecutive lanes");
+  bf16x8 qlo[QK_IPT], qhi[QK_IPT], doreg[DO_IPT], oreg[DO_IPT];
+  float lse_reg = INFINITY;
+  auto issue_loads = [&](int qbase0) {
+#pragma unroll
+    for (int j = 0; j < QK_IPT; ++j) {
+      const int idx = threadIdx.x + j * NT;
+      const int qrow = qbase0 + idx / PAIRS_PER_ROW;
+      const int c0 = (idx % PAIRS_PER_ROW) * 8;
+      const bool ok = idx < QK_ITEMS && qrow < N;
+      qlo[j] = ok ? load8(lay.at(in, qrow, 0, c0)) : bf16x8{};
+      qhi[j] = ok ? load8(lay.at(in, qrow, 0, c0 + HALF)) : bf16x8{};
+    }
+#pragma unroll
+    for (int j = 0; j < DO_IPT; ++j) {
+      const int idx = (int)threadIdx.x - DO_T0 + j * NT;
+      const int qrow = qbase0 + idx / PER_ROW;
+      const bool ok = idx >= 0 && idx < DO_ITEMS && qrow < N;
+      doreg[j] = ok ? load8(lay.o_row(dout, qrow) + (idx % PER_ROW) * 8) : bf16x8{};
+      oreg[j] = ok ? load8(lay.o_row(o, qrow) + (idx % PER_ROW) * 8) : bf16x8{};
+    }
+    if (threadIdx.x < QB) {
+      const int qrow = qbase0 + threadIdx.x;
+      lse_reg = (qrow < N) ? lse[c.stat_off + qrow] : INFINITY;
+    }
+  };
+  auto write_tile = [&](int qbase0) {
+#pragma unroll
+    for (int j = 0; j < QK_IPT; ++j) {
+      const int idx = threadIdx.x + j * NT;
+      if (idx < QK_ITEMS) {
+        const int lrow = idx / PAIRS_PER_ROW;
+        const int c0 = (idx % PAIRS_PER_ROW) * 8;
+        const int qrow = qbase0 + lrow;
+        const int p = qrow - c.prefix;
+        if (c.use_rope && qrow < N && p >= 0)
+          rope_rotate8(qlo[j], qhi[j], sin_t + (long)p * HD, cos_t + (long)p * HD, c0);
+        *reinterpret_cast<bf16x8*>(&q_lds[lrow * ROW_STRIDE + c0]) = qlo[j];
+        *reinterpret_cast<bf16x8*>(&q_lds[lrow * ROW_STRIDE + HALF + c0]) = qhi[j];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          qt_lds[(c0 + e) * T_STRIDE + lrow] = reinterpret_cast<__hip_bfloat16*>(&qlo[j])[e];
+          qt_lds[(c0 + HALF + e) * T_STRIDE + lrow] = reinterpret_cast<__hip_bfloat16*>(&qhi[j])[e];
+        }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < DO_IPT; ++j) {
+      const int idx = (int)threadIdx.x - DO_T0 + j * NT;
+      const int lrow = idx / PER_ROW;
+      const int c8 = (idx % PER_ROW) * 8;
+      // every lane takes part in the shuffles; chunks outside the slice hold zeros
+      float dsum = 0.f;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) dsum += b2f(doreg[j][e]) * b2f(oreg[j][e]);
+      dsum += __shfl_xor(dsum, 1, 64);
+      dsum += __shfl_xor(dsum, 2, 64);
+      dsum += __shfl_xor(dsum, 4, 64);
+      if (idx >= 0 && idx < DO_ITEMS) {
+        *reinterpret_cast<bf16x8*>(&do_lds[lrow * ROW_STRIDE + c8]) = doreg[j];
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+          dot_lds[(c8 + e) * T_STRIDE + lrow] = reinterpret_cast<__hip_bfloat16*>(&doreg[j])[e];
+        if (c8 == 0) d_lds[lrow] = dsum;
+      }
+    }
+    if (threadIdx.x < QB) lse_lds[threadIdx.x] = lse_reg;
+  };
+
+  // reduction map: TPR threads per q row, EPT columns of each half per thread
+  constexpr int TPR = NT / QB;
+  constexpr int EPT = HALF / TPR;
+  static_assert(TPR * EPT == HALF && EPT % 2 == 0);
+  const int red_q = threadIdx.x / TPR;
+  const int red_d = (threadIdx.x % TPR) * EPT;
+
+  const int n_q = (N + QB - 1) / QB;
+  issue_loads(0);
+  for (int qt = 0; qt < n_q; ++qt) {
+    const int qbase = qt * QB;
+    // the images' readers (compute of slice qt-1) finished before that
+    // slice's second barrier; the slots' readers finish before the next one
+    write_tile(qbase);
+    if (qt + 1 < n_q) issue_loads(qbase + QB);
+    __syncthreads();
+
+    if (wave_active) {
+      f32x16 s_acc = {}, dp_acc = {};
+#pragma unroll
+      for (int s = 0; s < KSLICES; ++s) {
+        const int a = l31 * ROW_STRIDE + s * 16 + hhalf * 8;
+        s_acc = MFMA32(load8(q_lds + a), kf[s], s_acc);
+        dp_acc = MFMA32(load8(do_lds + a), vf[s], dp_acc);
+      }
+      float pv[16], ds[16];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int lq = c_row(r, hhalf);
+        const bool valid = (qbase + lq < N) && (krow < N);
+        float p = valid ? __expf(s_acc[r] * scale - lse_lds[lq]) : 0.f;
+        pv[r] = p;
+        ds[r] = p * (dp_acc[r] - d_lds[lq]) * scale;
+      }
+      const bf16x8 p0 = pack_fragment(pv, 0);
+      const bf16x8 p1 = pack_fragment(pv, 8);
+      const bf16x8 s0 = pack_fragment(ds, 0);
+      const bf16x8 s1 = pack_fragment(ds, 8);
+      // dS[q = hhalf*8 + e (+16)][key = l31] -> ds_lds[q][key]
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        ds_lds[(hhalf * 8 + e) * T_STRIDE + l31] = reinterpret_cast<const __hip_bfloat16*>(&s0)[e];
+        ds_lds[(16 + hhalf * 8 + e) * T_STRIDE + l31] = reinterpret_cast<const __hip_bfloat16*>(&s1)[e];
+      }
+#pragma unroll
+      for (int t = 0; t < DTILES; ++t) {
+        // A[i = d = t*32 + l31][q = hhalf*8 + e] and the same 16 rows further
+        const int a0 = (t * 32 + l31) * T_STRIDE + hhalf * 8;
+        mfma2_acc(dv_acc[t], load8(dot_lds + a0), p0, load8(dot_lds + a0 + 16), p1);
+        mfma2_acc(dk_acc[t], load8(qt_lds + a0), s0, load8(qt_lds + a0 + 16), s1);
+      }
+      // partial dQ^T[d, q = l31] over this wave's keys: B[key = hhalf*8 + e (+16)][q]
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      const bf16x8 f0 = load8(ds_lds + l31 * T_STRIDE + hhalf * 8);
+      const bf16x8 f1 = load8(ds_lds + l31 * T_STRIDE + 16 + hhalf * 8);
+#pragma unroll
+      for (int t = 0; t < DTILES; ++t) {
+        f32x16 acc = {};
+        acc = MFMA32(ktf[t][0], f0, acc);
+        acc = MFMA32(ktf[t][1], f1, acc);
+        // regs 4g .. 4g+3 are d = t*32 + 8g + 4*hhalf + 0..3
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const float4_t v = {acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]};
+          *reinterpret_cast<float4_t*>(&my_slot[l31 * SLOT_STRIDE + t * 32 + 8 * g + 4 * hhalf]) = v;
+        }
+      }
+    }
+    __syncthreads();
+
+    // dQ[q, d] = slots added in wave order; columns (d, d + HALF) pair up in the rope
+    const int qrow = qbase + red_q;
+    if (qrow < N) {
+      float glo[EPT], ghi[EPT];
+#pragma unroll
+      for (int e = 0; e < EPT; ++e) glo[e] = ghi[e] = 0.f;
+      for (int w = 0; w < n_active; ++w) {
+        const float* sl = slots + w * Smem::SLOT_FLOATS + red_q * SLOT_STRIDE + red_d;
+#pragma unroll
+        for (int e = 0; e < EPT; ++e) {
+          glo[e] += sl[e];
+          ghi[e] += sl[HALF + e];
+        }
+      }
+      const int p = qrow - c.prefix;
+      if (c.use_rope && p >= 0) {
+        const float* srow = sin_t + (long)p * HD + red_d;
+        const float* crow = cos_t + (long)p * HD + red_d;
+#pragma unroll
+        for (int e = 0; e < EPT; ++e) {
+          const float co = crow[e], s = srow[e];
+          const float lo = glo[e], hi = ghi[e];
+          glo[e] = lo * co + hi * s;
+          ghi[e] = hi * co - lo * s;
+        }
+      }
+      __hip_bfloat16* row = lay.grad_row(grad, 0, qrow) + red_d;
+#pragma unroll
+      for (int e = 0; e < EPT; e += 2) {
+        *reinterpret_cast<unsigned*>(row + e) = pack2_bf16(glo[e], glo[e + 1]);
+        *reinterpret_cast<unsigned*>(row + HALF + e) = pack2_bf16(ghi[e], ghi[e + 1]);
+      }
+    }
+  }
+
+  // dK and dV rows: an accumulator holds one key per lane and d down the
+  // registers, which stored directly is 2 bytes per lane and row. They go
+  // through the wave's slot as [key][d] fp32 instead (the dQ partial's layout)
+  // and leave as 16-byte pieces, 8 lanes per 128-byte row.
+  __syncthreads();  // the last slice's reduction has read the slots
+  if (wave_active) {
+    if (krow < N) rope_inverse(dk_acc, sin_t, cos_t, krow, c);
+    auto store_via_slot = [&](const float (&acc)[DTILES][16], int which) {
+#pragma unroll
+      for (int t = 0; t < DTILES; ++t)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const float4_t v = {acc[t][4 * g], acc[t][4 * g + 1], acc[t][4 * g + 2], acc[t][4 * g + 3]};
+          *reinterpret_cast<float4_t*>(&my_slot[l31 * SLOT_STRIDE + t * 32 + 8 * g + 4 * hhalf]) = v;
+        }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+      for (int i = 0; i < 32 / 8; ++i) {
+        const int lk = i * 8 + c.lane / 8;
+        const int d0 = (c.lane & 7) * 8;
+        float v[8];
+        *reinterpret_cast<float4_t*>(v) = *reinterpret_cast<const float4_t*>(&my_slot[lk * SLOT_STRIDE + d0]);
+        *reinterpret_cast<float4_t*>(v + 4) =
+            *reinterpret_cast<const float4_t*>(&my_slot[lk * SLOT_STRIDE + d0 + 4]);
+        if (k0 + lk < N) Pack8<__hip_bfloat16>::store(lay.grad_row(grad, which, k0 + lk) + d0, v);
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    };
+    store_via_slot(dk_acc, 1);
+    store_via_slot(dv_acc, 2);
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Backward preprocess: D[b,h,n] = sum_d dO*O (fp32), rows ordered (b, h, n).
 // One wave per 8 rows: 8 lanes per row, 8 bf16 per lane per pass. (The name
 // dates from the token-major-only version; kept so traces stay comparable.)
@@ -864,7 +1206,44 @@ void launch_bwd_dkv(typename L::Qkv in, const __hip_bfloat16* dout, const float*
   }
 }
 
+template <class L, int HD, int NT, class... A>
+static void run_fused(dim3 grid, hipStream_t stream, A... args) {
+  using Smem = FusedBwdSmem<HD, NT>;
+  launch<bwd_fused_kernel<L, HD, NT>, Smem::BYTES, (Smem::BYTES > LDS_DEFAULT_MAX)>(
+      grid, NT, stream, args...);
+}
+
+// the shapes one workgroup holds: 8 waves of 32 keys each
+bool fused_bwd_supported(int N, int HD) {
+  return HD == 64 && N >= 1 && N <= FusedBwdSmem<64, 512>::MAX_N;
+}
+
+// DINOV3_FMHA_FUSED_BWD=0 forces the three-launch path (A/B runs, tests); read
+// per call like DINOV3_FMHA_DKV64
+bool fused_bwd_enabled() {
+  const char* v = getenv("DINOV3_FMHA_FUSED_BWD");
+  return !(v && v[0] == '0');
+}
+
+template <class L>
+void launch_bwd_fused(typename L::Qkv in, const __hip_bfloat16* dout, const __hip_bfloat16* o,
+                      const float* sin_t, const float* cos_t, const float* lse,
+                      typename L::DQkv grad, int B, int H, int N, int P, int HD, float scale,
+                      hipStream_t stream) {
+  // the kernel indexes one LDS slot per 32 keys: a longer sequence would run past them
+  if (!fused_bwd_supported(N, HD))
+    throw std::invalid_argument("launch_bwd_fused: shape outside fused_bwd_supported(N, HD)");
+  const dim3 grid(B * H);
+  if (small_n(N))
+    run_fused<L, 64, 128>(grid, stream, in, dout, o, sin_t, cos_t, lse, grad, B, H, N, P, scale);
+  else
+    run_fused<L, 64, 512>(grid, stream, in, dout, o, sin_t, cos_t, lse, grad, B, H, N, P, scale);
+}
+
 #define INSTANTIATE_LAUNCHERS(L)                                                            \
+  template void launch_bwd_fused<L>(L::Qkv, const __hip_bfloat16*, const __hip_bfloat16*,   \
+                                    const float*, const float*, const float*, L::DQkv, int, \
+                                    int, int, int, int, float, hipStream_t);                \
   template void launch_fwd<L>(L::Qkv, const float*, const float*, __hip_bfloat16*, float*,  \
                               int, int, int, int, int, float, hipStream_t);                 \
   template void launch_bwd_pre<L>(const __hip_bfloat16*, const __hip_bfloat16*, float*, int, \

@@ -36,15 +36,53 @@ def row(name, hip_us, ref_us, bytes_moved):
           f"x{ref_us / hip_us:5.2f}   {gbs:7.0f} GB/s")
 
 
+def fmha_bwd_rows(iters, rounds=5):
+    """The attention backward alone at the flagship student's two crop groups
+    (kept samples after drop-path), on an explicit dO, RoPE on, prefix 1:
+    the single-pass kernel against the three launches (pre + dq + dkv) in one
+    process, `rounds` alternating rounds each, median and minimum."""
+    from dinov3_amd.ops import hip_ops
+
+    ops = hip_ops()
+    dev = "cuda"
+    for B, N, Hh, hd in ((89, 197, 16, 64), (358, 37, 16, 64)):
+        qkv = torch.randn(B, N, 3, Hh, hd, device=dev).bfloat16()
+        dout = torch.randn(B, N, Hh, hd, device=dev).bfloat16()
+        a = torch.rand(N - 1, hd // 2, device=dev)
+        a = torch.cat([a, a], dim=-1)
+        sin, cos = a.sin().contiguous(), a.cos().contiguous()
+        o, lse = ops.fmha_rope_fwd(qkv, sin, cos, 1)
+        dqkv = torch.empty_like(qkv)
+        times = {"1": [], "0": []}
+        saved = os.environ.get("DINOV3_FMHA_FUSED_BWD")
+        for _ in range(rounds):
+            for flag in ("1", "0"):  # the bindings read the switch at every call
+                os.environ["DINOV3_FMHA_FUSED_BWD"] = flag
+                times[flag].append(timeit(
+                    lambda: ops.fmha_rope_bwd_out(dout, qkv, o, lse, sin, cos, 1, dqkv), iters))
+        if saved is None:
+            del os.environ["DINOV3_FMHA_FUSED_BWD"]
+        else:
+            os.environ["DINOV3_FMHA_FUSED_BWD"] = saved
+        med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
+        print(f"{f'fmha_rope_bwd [{B},{N},{Hh},{hd}]':34s} fused {med['1']:7.1f} us (min {min(times['1']):7.1f})   "
+              f"three-launch {med['0']:7.1f} us (min {min(times['0']):7.1f})   x{med['0'] / med['1']:5.2f}")
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--iters", type=int, default=50)
+    p.add_argument("--fmha-bwd-only", action="store_true",
+                   help="only the attention-backward rows (single pass against three launches)")
     p.add_argument("--streaming-only", action="store_true",
                    help="stop after the memory-streaming kernels (norms, bias+GELU, LayerScale)")
     args = p.parse_args()
     assert torch.cuda.is_available(), "GPU required"
     dev = "cuda"
     it = args.iters
+    if args.fmha_bwd_only:
+        fmha_bwd_rows(it)
+        return
 
     # ViT-L flat-buffer shapes: R = 2*64*197 + 8*64*37 tokens, D = 1024
     R, D = 2 * 64 * 197 + 8 * 64 * 37, 1024
@@ -235,6 +273,8 @@ def main():
         timeit(fmha2_fwd_bwd, max(it // 4, 3)),
         timeit(sdpa2_fwd_bwd, max(it // 4, 3)),
         B2 * N2 * 3 * Hh2 * hd2 * 2 * 6)
+
+    fmha_bwd_rows(it)
 
     # fused sinkhorn over K=65536 (teacher shapes: M=128 cls rows)
     from dinov3_amd.ops.proto_scores import sinkhorn_knopp_factored
