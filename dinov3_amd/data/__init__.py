@@ -1,6 +1,7 @@
 from .augmentations import DataAugmentationDINO
 from .collate import collate_data_and_cast, get_batch_subset
-from .datasets import ADE20K, CocoCaptions, ImageNet, ImageNet22k, Split, SyntheticDataset
+from .datasets import (ADE20K, CocoCaptions, ImageNet, ImageNet22k, Split, SyntheticDataset,
+                       SyntheticSeg)
 from .loaders import SamplerType, make_data_loader, make_dataset
 from .masking import MaskingGenerator
 from .samplers import EpochSampler, InfiniteSampler, ShardedInfiniteSampler
@@ -21,5 +22,6 @@ __all__ = [
     "ADE20K",
     "CocoCaptions",
     "SyntheticDataset",
+    "SyntheticSeg",
     "Split",
 ]

@@ -212,3 +212,43 @@ class SyntheticDataset(_SyntheticSplitDataset):
 
     def decode_image(self, data, index: int) -> torch.Tensor:
         return random_image(self.height, self.width)
+
+
+class SyntheticSeg(_SyntheticSplitDataset):
+    """Synthetic dense-label dataset whose image carries the class, so that a
+    segmentation probe has something to learn offline. Sample `index` (seeded
+    by split and index, the same on every visit) has a label map of
+    GRID x GRID square regions, each of one of NUM_CLASSES classes, with about
+    2 % of the pixels set to 255 (ignored); its image fills every region with
+    the colour of its class plus noise."""
+
+    NAME = "SyntheticSeg"
+    NUM_CLASSES = 5
+    GRID = 4
+    _COLOURS = ((0.9, 0.1, 0.1), (0.1, 0.9, 0.1), (0.1, 0.1, 0.9), (0.9, 0.9, 0.1),
+                (0.1, 0.9, 0.9))
+
+    def __init__(self, split: Split = Split.TRAIN, root: str = "", extra: str = "",
+                 transform=None, target_transform=None, length: int = 1024, size: int = 64):
+        super().__init__(split, root, extra, transform, target_transform, length=length)
+        assert size % self.GRID == 0, "size must be a multiple of the region grid"
+        self.size = size
+
+    def _rng(self, index: int, stream: int) -> np.random.Generator:
+        return np.random.default_rng([list(Split).index(self.split), index, stream])
+
+    def _label_map(self, index: int) -> np.ndarray:
+        region = self.size // self.GRID
+        coarse = self._rng(index, 0).integers(0, self.NUM_CLASSES, size=(self.GRID, self.GRID))
+        return np.kron(coarse, np.ones((region, region), dtype=np.int64))
+
+    def decode_image(self, data, index: int) -> torch.Tensor:
+        colours = np.asarray(self._COLOURS, dtype=np.float32)[self._label_map(index)]  # [H, W, 3]
+        noise = self._rng(index, 1).normal(0.0, 0.05, size=colours.shape).astype(np.float32)
+        img = np.clip(colours + noise, 0.0, 1.0).transpose(2, 0, 1)
+        return torch.from_numpy(np.ascontiguousarray(img))
+
+    def get_target(self, index: int) -> torch.Tensor:
+        classes = self._label_map(index)
+        classes[self._rng(index, 2).random(classes.shape) < 0.02] = 255
+        return torch.from_numpy(classes)

@@ -31,6 +31,7 @@ _DATASETS = {
     "ADE20K": ds.ADE20K,
     "CocoCaptions": ds.CocoCaptions,
     "Synthetic": ds.SyntheticDataset,
+    "SyntheticSeg": ds.SyntheticSeg,
 }
 
 

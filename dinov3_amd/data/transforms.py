@@ -211,6 +211,35 @@ def make_classification_train_transform(crop_size: int = 224, hflip_prob: float 
     return _t
 
 
+def make_segmentation_transforms(crop_size: int = 512, mean=(0.485, 0.456, 0.406),
+                                 std=(0.229, 0.224, 0.225), reduce_zero_label: bool = False):
+    """Fixed square crops for the linear segmentation probe: returns
+    (image transform, target transform). The image is resized bilinearly to
+    crop_size x crop_size and normalised; the label map [H, W] is resized by
+    nearest neighbour and cast to uint8, 255 marking ignored pixels. With
+    `reduce_zero_label`, the ADE20K convention, 0 ("other") becomes 255 and
+    class k becomes k - 1."""
+
+    def _image(img: torch.Tensor) -> torch.Tensor:
+        img = F.interpolate(img.unsqueeze(0), size=(crop_size, crop_size), mode="bilinear",
+                            align_corners=False, antialias=True).squeeze(0).clamp(0.0, 1.0)
+        return normalize(img, mean, std)
+
+    def _target(label) -> torch.Tensor:
+        label = torch.as_tensor(label)
+        if label.dim() != 2:
+            raise ValueError(f"segmentation target must be a [H, W] label map, got "
+                             f"{tuple(label.shape)}")
+        label = F.interpolate(label[None, None].float(), size=(crop_size, crop_size),
+                              mode="nearest")[0, 0].long()
+        if reduce_zero_label:
+            label = torch.where(label == 0, torch.full_like(label, 255), label - 1)
+            label = torch.where(label == 254, torch.full_like(label, 255), label)  # 255 stays
+        return label.to(torch.uint8)
+
+    return _image, _target
+
+
 def voc2007_classification_target_transform(label, n_categories: int = 20) -> torch.Tensor:
     """Multi-label one-hot from a VOC-style label with .instances
     (reference transforms.py:153-157)."""

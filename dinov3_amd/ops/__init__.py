@@ -33,8 +33,12 @@ from .fp8_linear import (fp8_bwd_eligible, fp8_eligible, fp8_linear, fp8_quantiz
                          fp8_quantize_rows)
 from .knn import knn_topk, knn_topk_ref
 from .linear_probe import probe_ce, probe_ce_ref, probe_sgd_, probe_sgd_ref_
+from .seg_probe import SEG_MAX_CLASSES, seg_ce, seg_ce_ref
 
 __all__ = [
+    "seg_ce",
+    "seg_ce_ref",
+    "SEG_MAX_CLASSES",
     "probe_ce",
     "probe_ce_ref",
     "probe_sgd_",

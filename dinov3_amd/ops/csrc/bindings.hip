@@ -127,6 +127,12 @@ void launch_probe_ce(T*, const float*, const long*, float*, float*, long, int, i
 template <typename GT>
 void launch_probe_sgd(float*, float*, const GT*, const float*, const float*, __hip_bfloat16*, int,
                       long, float, float, hipStream_t);
+int seg_ce_quad_blocks(long, int);
+int seg_ce_fin_rows(long);
+template <typename T>
+void launch_seg_ce(T*, const float*, const unsigned char*, float*, float*, int*, float*, float*,
+                   long*, float*, const float*, long, int, int, int, int, int, int, float, bool,
+                   int, hipStream_t);
 int knn_topk_auto_splits(long, long);
 void launch_knn_topk(const __hip_bfloat16*, const __hip_bfloat16*, unsigned long long*, float*,
                      int*, long, long, int, int, int, hipStream_t);
@@ -1485,6 +1491,105 @@ void probe_sgd_(torch::Tensor w, torch::Tensor mom, torch::Tensor grad, torch::T
                                      current_stream());
 }
 
+// Linear segmentation probe: logits [M, h, w, G, Cp] (+ bias [G, Cp]) upsampled
+// bilinearly (align_corners = False) by the even factor s = H / h = W / w to the
+// labels [M, H, W] uint8, softmax cross-entropy over the first C columns per
+// pixel, 255 = ignored. Returns (loss_sum [G] fp32, areas [G, 3, Cp] int64:
+// intersection, prediction and label counts) and, with write_grad, dbias [G, Cp]
+// fp32 after the gradient with respect to the logits, times grad_scale (times
+// scale[0] when the one-element device tensor `scale` is given), has replaced
+// them in place.
+std::vector<torch::Tensor> seg_ce(torch::Tensor logits, c10::optional<torch::Tensor> bias,
+                                  torch::Tensor labels, int64_t C, double grad_scale,
+                                  bool write_grad, c10::optional<torch::Tensor> scale) {
+  CHECK_INPUT(logits);
+  CHECK_INPUT(labels);
+  TORCH_CHECK(logits.dim() == 5, "seg_ce: logits must be [M, h, w, G, Cp]");
+  TORCH_CHECK(logits.scalar_type() == at::ScalarType::BFloat16 ||
+                  logits.scalar_type() == at::ScalarType::Float,
+              "seg_ce: logits must be bf16 or fp32");
+  TORCH_CHECK(labels.scalar_type() == at::ScalarType::Byte && labels.dim() == 3 &&
+                  labels.size(0) == logits.size(0),
+              "seg_ce: labels must be uint8 [M, H, W]");
+  TORCH_CHECK(labels.device() == logits.device(), "seg_ce: labels and logits must be on one device");
+  const long M = logits.size(0), h = logits.size(1), w = logits.size(2);
+  const long G = logits.size(3), Cp = logits.size(4);
+  const long H = labels.size(1), W = labels.size(2);
+  TORCH_CHECK(h >= 1 && w >= 1 && h <= 4096 && w <= 4096, "seg_ce: h and w must be in [1, 4096]");
+  const long s = H / h;
+  TORCH_CHECK(H == s * h && W == s * w, "seg_ce: need H = s h and W = s w with one integer s, got ",
+              H, " x ", W, " labels for ", h, " x ", w, " cells");
+  TORCH_CHECK(s % 2 == 0 && s >= 2 && s <= SEG_MAX_SCALE, "seg_ce: the scale must be even and in [2, ",
+              SEG_MAX_SCALE, "], got ", s);
+  TORCH_CHECK(Cp > 0 && Cp % 8 == 0 && Cp <= SEG_MAX_CP,
+              "seg_ce: Cp must be a positive multiple of 8 and at most ", SEG_MAX_CP, ", got ", Cp);
+  TORCH_CHECK(C >= 1 && C <= Cp && C <= SEG_MAX_CLASSES, "seg_ce: need 1 <= C <= min(Cp, ",
+              SEG_MAX_CLASSES, "), got C = ", C, ", Cp = ", Cp);
+  TORCH_CHECK(G >= 1 && G <= 65535, "seg_ce: G must be in [1, 65535], got ", G);
+  TORCH_CHECK(M * H * W < (1L << 31), "seg_ce: M H W must be below 2^31 (block counts are int32)");
+  TORCH_CHECK(G * Cp <= INT_MAX, "seg_ce: G Cp must fit an int");
+  TORCH_CHECK((uintptr_t)logits.data_ptr() % 16 == 0, "seg_ce: logits must be 16-byte aligned");
+  // the labels are read a byte at a time: a slice of images needs no alignment
+  const float* bias_ptr = nullptr;
+  if (bias.has_value()) {
+    const torch::Tensor& b = *bias;
+    CHECK_INPUT(b);
+    TORCH_CHECK(b.scalar_type() == at::ScalarType::Float && b.dim() == 2 && b.size(0) == G &&
+                    b.size(1) == Cp,
+                "seg_ce: bias must be fp32 [G, Cp]");
+    TORCH_CHECK(b.device() == logits.device(), "seg_ce: bias and logits must be on one device");
+    TORCH_CHECK((uintptr_t)b.data_ptr() % 16 == 0, "seg_ce: bias must be 16-byte aligned");
+    bias_ptr = b.data_ptr<float>();
+  }
+  const float* scale_ptr = nullptr;
+  if (scale.has_value()) {
+    const torch::Tensor& sc = *scale;
+    CHECK_INPUT(sc);
+    TORCH_CHECK(sc.scalar_type() == at::ScalarType::Float && sc.numel() == 1 &&
+                    sc.device() == logits.device(),
+                "seg_ce: scale must be one fp32 value on the logits' device");
+    scale_ptr = sc.data_ptr<float>();
+  }
+  auto fopts = logits.options().dtype(torch::kFloat);
+  if (M == 0) {
+    std::vector<torch::Tensor> ret = {torch::zeros({G}, fopts),
+                                      torch::zeros({G, 3, Cp}, fopts.dtype(torch::kLong))};
+    if (write_grad) ret.push_back(torch::zeros({G, Cp}, fopts));
+    return ret;
+  }
+  const long quads = M * h * w;
+  const int nblk = seg_ce_quad_blocks(quads, (int)G);
+  auto loss = torch::empty({G}, fopts);
+  auto areas = torch::empty({G, 3, Cp}, fopts.dtype(torch::kLong));
+  auto part_loss = torch::empty({(long)nblk, G}, fopts);
+  auto part_area = torch::empty({(long)nblk, G, 3, Cp}, fopts.dtype(torch::kInt));
+  torch::Tensor ws, part_db, dbias;
+  if (write_grad) {
+    ws = torch::empty({quads, 4, G, Cp}, fopts);
+    part_db = torch::empty({(long)seg_ce_fin_rows(quads), G * Cp}, fopts);
+    dbias = torch::empty({G, Cp}, fopts);
+  }
+  float* ws_ptr = write_grad ? ws.data_ptr<float>() : nullptr;
+  float* pdb_ptr = write_grad ? part_db.data_ptr<float>() : nullptr;
+  float* db_ptr = write_grad ? dbias.data_ptr<float>() : nullptr;
+  if (logits.scalar_type() == at::ScalarType::Float)
+    launch_seg_ce<float>(logits.data_ptr<float>(), bias_ptr, labels.data_ptr<uint8_t>(), ws_ptr,
+                         part_loss.data_ptr<float>(), part_area.data_ptr<int>(), pdb_ptr,
+                         loss.data_ptr<float>(), areas.data_ptr<long>(), db_ptr, scale_ptr, M,
+                         (int)h, (int)w, (int)s, (int)G, (int)Cp, (int)C, (float)grad_scale,
+                         write_grad, nblk, current_stream());
+  else
+    launch_seg_ce<__hip_bfloat16>((__hip_bfloat16*)logits.data_ptr(), bias_ptr,
+                                  labels.data_ptr<uint8_t>(), ws_ptr, part_loss.data_ptr<float>(),
+                                  part_area.data_ptr<int>(), pdb_ptr, loss.data_ptr<float>(),
+                                  areas.data_ptr<long>(), db_ptr, scale_ptr, M, (int)h, (int)w,
+                                  (int)s, (int)G, (int)Cp, (int)C, (float)grad_scale, write_grad,
+                                  nblk, current_stream());
+  std::vector<torch::Tensor> ret = {loss, areas};
+  if (write_grad) ret.push_back(dbias);
+  return ret;
+}
+
 }  // namespace
 
 // hipBLASLt fused-epilogue entry points (blaslt_ext.hip)
@@ -1552,6 +1657,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("C"), py::arg("grad_scale"), py::arg("write_grad"), py::arg("row_blocks") = 0);
   mod.def("probe_sgd_", &probe_sgd_, py::arg("w"), py::arg("mom"), py::arg("grad"), py::arg("lr"),
           py::arg("wd"), py::arg("lr_scale"), py::arg("momentum"), py::arg("w_lp"));
+  mod.def("seg_ce", &seg_ce, py::arg("logits"), py::arg("bias"), py::arg("labels"), py::arg("C"),
+          py::arg("grad_scale"), py::arg("write_grad"), py::arg("scale") = py::none());
+  mod.attr("SEG_MAX_CLASSES") = SEG_MAX_CLASSES;
   mod.def("fmha_fwd", &fmha_fwd);
   mod.def("fmha_rope_fwd", [](torch::Tensor qkv, torch::Tensor sin_t, torch::Tensor cos_t,
                               int64_t prefix) {

@@ -223,7 +223,12 @@ static inline void launch_colreduce_finalize(const float* part0, T* out0, const 
 #define FP8_COLS_SLICES 32         // pass 1: row slices per block
 #define FP8_COLS_MAX_PARTIALS 256  // pass 1: partial rows of the [partials, C] workspace
 
-#define HIP_CHECK_LAUNCH()                                                    \
+// ---- segmentation probe (seg_probe.hip) ----
+#define SEG_MAX_CLASSES 255  // labels are uint8 and 255 marks an ignored pixel
+#define SEG_MAX_CP 256       // padded class count: four classes per lane
+#define SEG_MAX_SCALE 32     // label pixels per cell along an axis
+
+#define HIP_CHECK_LAUNCH()                                                   \
   do {                                                                        \
     hipError_t e = hipGetLastError();                                         \
     if (e != hipSuccess) {                                                    \

@@ -509,7 +509,37 @@ def do_test(cfg, model, iteration: int):
         results["knn_top1"] = evaluate_knn(train_feats, train_labels, val_feats, val_labels)
         results["linear_top1"] = evaluate_linear_probe(train_feats, train_labels, val_feats,
                                                        val_labels)
+    seg_base = os.environ.get("DINOV3_EVAL_SEG", "")
+    if seg_base:
+        results.update(_seg_probe_results(cfg, backbone, seg_base, kwargs))
     logger.info("eval results: %s", results)
+    return results
+
+
+def _seg_probe_results(cfg, backbone, base: str, loader_kwargs) -> dict:
+    """The dense half of do_test, behind DINOV3_EVAL_SEG=<dataset string base>
+    (`SyntheticSeg`, or `ADE20K:root=...`): patch features at
+    crops.global_crops_size, then the linear segmentation probe's lr grid."""
+    from ..data import make_data_loader, make_dataset
+    from ..data.transforms import make_segmentation_transforms
+    from ..eval import evaluate_segmentation_linear, extract_dense_features
+
+    name = base.split(":")[0]
+    transform, target_transform = make_segmentation_transforms(
+        crop_size=cfg.crops.global_crops_size, mean=cfg.crops.rgb_mean, std=cfg.crops.rgb_std,
+        reduce_zero_label=name == "ADE20K")
+    sizes = {"TRAIN": ":length=256", "VAL": ":length=64"} if name == "SyntheticSeg" else {}
+    sets = []
+    for split in ("TRAIN", "VAL"):
+        dataset = make_dataset(dataset_str=f"{base}:split={split}{sizes.get(split, '')}",
+                               transform=transform, target_transform=target_transform)
+        sets.append(extract_dense_features(
+            backbone, make_data_loader(dataset=dataset, **loader_kwargs), to_cpu=False))
+    probe = evaluate_segmentation_linear(*sets[0], *sets[1], num_classes=dataset.NUM_CLASSES)
+    best = probe["best_head"]
+    results = {"seg_miou": probe["best_miou"], "seg_pixel_acc": probe["pixel_acc"][best],
+               "seg_best_lr": probe["heads"][best][0]}
+    results.update({f"seg_miou_head{i}": v for i, v in enumerate(probe["miou"])})
     return results
 
 
