@@ -34,8 +34,12 @@ from .fp8_linear import (fp8_bwd_eligible, fp8_eligible, fp8_linear, fp8_quantiz
 from .knn import knn_topk, knn_topk_ref
 from .linear_probe import probe_ce, probe_ce_ref, probe_sgd_, probe_sgd_ref_
 from .seg_probe import SEG_MAX_CLASSES, seg_ce, seg_ce_ref
+from .gram_loss import GRAM_DEFAULT_PANEL_BYTES, gram_loss, gram_loss_ref
 
 __all__ = [
+    "gram_loss",
+    "gram_loss_ref",
+    "GRAM_DEFAULT_PANEL_BYTES",
     "seg_ce",
     "seg_ce_ref",
     "SEG_MAX_CLASSES",

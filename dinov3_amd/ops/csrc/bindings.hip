@@ -136,6 +136,13 @@ void launch_seg_ce(T*, const float*, const unsigned char*, float*, float*, int*,
 int knn_topk_auto_splits(long, long);
 void launch_knn_topk(const __hip_bfloat16*, const __hip_bfloat16*, unsigned long long*, float*,
                      int*, long, long, int, int, int, hipStream_t);
+void launch_gram_rnorm(const __hip_bfloat16*, const __hip_bfloat16*, float*, long, int, bool,
+                       hipStream_t);
+void launch_gram_tiles(const __hip_bfloat16*, const __hip_bfloat16*, const float*, const float*,
+                       __hip_bfloat16*, float*, int, int, int, long, int, hipStream_t);
+void launch_gram_finish(const float*, float*, long, double, hipStream_t);
+void launch_gram_norm_bwd(const __hip_bfloat16*, const __hip_bfloat16*, const float*,
+                          __hip_bfloat16*, long, int, float, bool, hipStream_t);
 template <typename T>
 void launch_multi_tensor_ema(T* const*, const T* const*, const long*, const int*,
                              const long*, int, float, hipStream_t);
@@ -1590,6 +1597,114 @@ std::vector<torch::Tensor> seg_ce(torch::Tensor logits, c10::optional<torch::Ten
   return ret;
 }
 
+// ------------------------------ Gram loss --------------------------------
+// The pieces of ops.gram_loss (gram_loss.hip); the panel loop and the P @ S
+// GEMM between them are in ops/gram_loss.py.
+
+constexpr long kGramTile = 128;
+
+void check_gram_inputs(const torch::Tensor& student, const torch::Tensor& teacher) {
+  CHECK_INPUT(student);
+  CHECK_INPUT(teacher);
+  TORCH_CHECK(student.scalar_type() == at::ScalarType::BFloat16 &&
+                  teacher.scalar_type() == at::ScalarType::BFloat16,
+              "gram_loss: student and teacher must be bf16");
+  TORCH_CHECK(student.dim() == 3, "gram_loss: student must be [G, M, D]");
+  TORCH_CHECK(teacher.sizes() == student.sizes(), "gram_loss: student and teacher must have one "
+              "shape, got ", student.sizes(), " and ", teacher.sizes());
+  TORCH_CHECK(student.device() == teacher.device(),
+              "gram_loss: student and teacher must be on one device");
+  const long G = student.size(0), M = student.size(1), D = student.size(2);
+  TORCH_CHECK(G >= 1 && M >= 1, "gram_loss: need G >= 1 and M >= 1");
+  TORCH_CHECK(D >= 8 && D % 8 == 0 && D <= (1 << 20),
+              "gram_loss: D must be a positive multiple of 8, got ", D);
+  TORCH_CHECK(M <= (1L << 30) && G * M <= (1L << 40), "gram_loss: M or G M too large");
+  TORCH_CHECK((uintptr_t)student.data_ptr() % 16 == 0 && (uintptr_t)teacher.data_ptr() % 16 == 0,
+              "gram_loss: student and teacher must be 16-byte aligned");
+}
+
+// r [2, G M] fp32: rsqrt of the squared row norms of student (0) and teacher
+// (1), or ones without apply_norm.
+torch::Tensor gram_rnorm(torch::Tensor student, torch::Tensor teacher, bool apply_norm) {
+  check_gram_inputs(student, teacher);
+  const long rows = student.size(0) * student.size(1);
+  auto r = torch::empty({2, rows}, student.options().dtype(torch::kFloat));
+  launch_gram_rnorm((const __hip_bfloat16*)student.data_ptr(),
+                    (const __hip_bfloat16*)teacher.data_ptr(), r.data_ptr<float>(), rows,
+                    (int)student.size(2), apply_norm, current_stream());
+  return r;
+}
+
+// Row tiles tile0 .. tile0 + ntiles - 1 (of the G * nT row tiles of 128 rows,
+// nT = ceil(M / 128)) of both similarity matrices: their loss partials go to
+// partials [G * nT * nT] and, with a panel [>= ntiles * 128, nT * 128] bf16,
+// P = e * mask * r_j of those rows to it. mode: 0 plain, 1 remove_neg,
+// 2 remove_only_teacher_neg.
+void gram_tiles(torch::Tensor student, torch::Tensor teacher, torch::Tensor r, int64_t mode,
+                int64_t tile0, int64_t ntiles, c10::optional<torch::Tensor> panel,
+                torch::Tensor partials) {
+  check_gram_inputs(student, teacher);
+  const long G = student.size(0), M = student.size(1), D = student.size(2);
+  const long nT = (M + kGramTile - 1) / kGramTile;
+  CHECK_INPUT(r);
+  CHECK_INPUT(partials);
+  TORCH_CHECK(r.scalar_type() == at::ScalarType::Float && r.dim() == 2 && r.size(0) == 2 &&
+                  r.size(1) == G * M && r.device() == student.device(),
+              "gram_tiles: r must be fp32 [2, G M] on the inputs' device");
+  TORCH_CHECK(partials.scalar_type() == at::ScalarType::Float && partials.numel() == G * nT * nT &&
+                  partials.device() == student.device(),
+              "gram_tiles: partials must be fp32 with G nT nT elements on the inputs' device");
+  TORCH_CHECK(mode >= 0 && mode <= 2, "gram_tiles: mode must be 0, 1 or 2");
+  TORCH_CHECK(ntiles >= 1 && ntiles <= 65535 && tile0 >= 0 && tile0 + ntiles <= G * nT,
+              "gram_tiles: row tiles [", tile0, ", ", tile0 + ntiles, ") are not inside [0, ",
+              G * nT, ") or are more than 65535");
+  __hip_bfloat16* p_ptr = nullptr;
+  if (panel.has_value()) {
+    const torch::Tensor& p = panel.value();
+    CHECK_INPUT(p);
+    TORCH_CHECK(p.scalar_type() == at::ScalarType::BFloat16 && p.dim() == 2 &&
+                    p.size(0) >= ntiles * kGramTile && p.size(1) == nT * kGramTile &&
+                    p.device() == student.device(),
+                "gram_tiles: panel must be bf16 [>= ntiles * 128, nT * 128] on the inputs' device");
+    TORCH_CHECK((uintptr_t)p.data_ptr() % 16 == 0, "gram_tiles: panel must be 16-byte aligned");
+    p_ptr = (__hip_bfloat16*)p.data_ptr();
+  }
+  launch_gram_tiles((const __hip_bfloat16*)student.data_ptr(),
+                    (const __hip_bfloat16*)teacher.data_ptr(), r.data_ptr<float>(),
+                    r.data_ptr<float>() + G * M, p_ptr, partials.data_ptr<float>(), (int)M, (int)D,
+                    (int)mode, tile0, (int)ntiles, current_stream());
+}
+
+// loss (0-dim fp32) = sum of the partials in a fixed order / count.
+torch::Tensor gram_finish(torch::Tensor partials, double count) {
+  CHECK_INPUT(partials);
+  TORCH_CHECK(partials.scalar_type() == at::ScalarType::Float && partials.numel() >= 1,
+              "gram_finish: partials must be fp32 and not empty");
+  TORCH_CHECK(count >= 1.0, "gram_finish: count must be at least 1");
+  auto loss = torch::empty({}, partials.options());
+  launch_gram_finish(partials.data_ptr<float>(), loss.data_ptr<float>(), partials.numel(), count,
+                     current_stream());
+  return loss;
+}
+
+// dS [G, M, D] bf16 from Draw = P @ S: c r_i (Draw_i - s^_i (s^_i . Draw_i)),
+// or c Draw_i without apply_norm.
+torch::Tensor gram_norm_bwd(torch::Tensor draw, torch::Tensor student, torch::Tensor r, double c,
+                            bool apply_norm) {
+  check_gram_inputs(student, draw);
+  CHECK_INPUT(r);
+  const long rows = student.size(0) * student.size(1);
+  TORCH_CHECK(r.scalar_type() == at::ScalarType::Float && r.dim() == 2 && r.size(0) == 2 &&
+                  r.size(1) == rows && r.device() == student.device(),
+              "gram_norm_bwd: r must be fp32 [2, G M] on the inputs' device");
+  auto ds = torch::empty_like(student);
+  launch_gram_norm_bwd((const __hip_bfloat16*)draw.data_ptr(),
+                       (const __hip_bfloat16*)student.data_ptr(), r.data_ptr<float>(),
+                       (__hip_bfloat16*)ds.data_ptr(), rows, (int)student.size(2), (float)c,
+                       apply_norm, current_stream());
+  return ds;
+}
+
 }  // namespace
 
 // hipBLASLt fused-epilogue entry points (blaslt_ext.hip)
@@ -1660,6 +1775,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("seg_ce", &seg_ce, py::arg("logits"), py::arg("bias"), py::arg("labels"), py::arg("C"),
           py::arg("grad_scale"), py::arg("write_grad"), py::arg("scale") = py::none());
   mod.attr("SEG_MAX_CLASSES") = SEG_MAX_CLASSES;
+  mod.def("gram_rnorm", &gram_rnorm, py::arg("student"), py::arg("teacher"),
+          py::arg("apply_norm"));
+  mod.def("gram_tiles", &gram_tiles, py::arg("student"), py::arg("teacher"), py::arg("r"),
+          py::arg("mode"), py::arg("tile0"), py::arg("ntiles"), py::arg("panel"),
+          py::arg("partials"));
+  mod.def("gram_finish", &gram_finish, py::arg("partials"), py::arg("count"));
+  mod.def("gram_norm_bwd", &gram_norm_bwd, py::arg("draw"), py::arg("student"), py::arg("r"),
+          py::arg("c"), py::arg("apply_norm"));
   mod.def("fmha_fwd", &fmha_fwd);
   mod.def("fmha_rope_fwd", [](torch::Tensor qkv, torch::Tensor sin_t, torch::Tensor cos_t,
                               int64_t prefix) {
