@@ -88,12 +88,7 @@ def _load_hip():
 
         _hip_mod = _hip_ops
     except ImportError:
-        try:
-            import importlib
-
-            _hip_mod = importlib.import_module("dinov3_amd.ops._hip_ops")
-        except ImportError:
-            _hip_mod = None
+        _hip_mod = None
     return _hip_mod
 
 

@@ -26,6 +26,8 @@
 #include <unordered_map>
 #include <vector>
 
+#include "blaslt_ext.h"
+
 namespace blaslt {
 
 #define HIPBLASLT_CHECK(expr)                                                   \
@@ -150,8 +152,6 @@ void check_2d_bf16(const torch::Tensor& t, const char* name) {
               name, " must be contiguous 2-D bf16 on GPU");
 }
 
-// h = gelu_tanh(x @ w^T + bias), pre-activation saved as aux.
-// x [M,K], w [N,K], bias [N]  ->  {h [M,N], pre [M,N]}
 std::vector<torch::Tensor> gemm_bias_gelu_fwd(torch::Tensor x, torch::Tensor w,
                                               torch::Tensor bias) {
   check_2d_bf16(x, "x");
@@ -170,8 +170,6 @@ std::vector<torch::Tensor> gemm_bias_gelu_fwd(torch::Tensor x, torch::Tensor w,
   return {h, pre};
 }
 
-// dpre = dgelu_tanh(dy @ w2, pre); dbias1 = column-sum of dpre (fp32).
-// dy [M,N2], w2 [N2,N1], pre [M,N1]  ->  {dpre [M,N1], dbias1 [N1] fp32}
 std::vector<torch::Tensor> gemm_dgelu_bgrad(torch::Tensor dy, torch::Tensor w2,
                                             torch::Tensor pre) {
   check_2d_bf16(dy, "dy");
@@ -190,7 +188,6 @@ std::vector<torch::Tensor> gemm_dgelu_bgrad(torch::Tensor dy, torch::Tensor w2,
   return {dpre, dbias};
 }
 
-// Plain bias GEMM, for validating the layout mapping: y = x @ w^T + bias.
 torch::Tensor gemm_bias(torch::Tensor x, torch::Tensor w, torch::Tensor bias) {
   check_2d_bf16(x, "x");
   check_2d_bf16(w, "w");
@@ -203,9 +200,6 @@ torch::Tensor gemm_bias(torch::Tensor x, torch::Tensor w, torch::Tensor bias) {
   return y;
 }
 
-// Probe: how many heuristic algorithms exist for a given epilogue/dtype combo
-// on this hardware (no matmul is run). aux_type/bias_type: hipDataType ints,
-// -1 = leave unset. Returns n_results (0 = unsupported combo).
 int probe_epilogue(int64_t epi, int64_t aux_type, int64_t bias_type,
                    int64_t m, int64_t n, int64_t k) {
   hipblasLtMatmulDesc_t op;

@@ -1,7 +1,7 @@
 // Fused elementwise kernels: bias+GELU (K8 epilogue), SwiGLU gate (K9),
 // RoPE rotate-half application (K5).
 
-#include "common.h"
+#include "elementwise.h"
 
 #define EW_BLOCK 256
 // The column-reduction backward kernels (bias_gelu_bwd, ls_*_bwd) run
@@ -533,8 +533,6 @@ void launch_bias_gelu_fwd(const T* x, const T* bias, T* y, long rows, int H,
                      dim3(EW_BLOCK), 0, stream, x, bias, y, rows, H, g.tpr);
 }
 
-// The *_bwd launchers below take `ws`, an fp32 workspace of COLRED_MAX_PARTIALS
-// rows of D per parameter gradient, and write each gradient in T.
 template <typename T>
 void launch_bias_gelu_bwd(const T* dy, const T* x, const T* bias, T* dx, float* ws,
                           T* dbias, long rows, int H, hipStream_t stream) {

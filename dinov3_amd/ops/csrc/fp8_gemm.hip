@@ -35,7 +35,7 @@
 // With unit block scales any k-order inside the 128-deep step gives the same
 // sum as long as A and B use the same one; both come from the same code here.
 
-#include "common.h"
+#include "fp8_gemm.h"
 
 typedef __attribute__((ext_vector_type(8))) int int8v_t;
 typedef __attribute__((ext_vector_type(4))) int int4v_t;
@@ -353,9 +353,6 @@ int fp8_cols_partials(long R, int C) {
   return (int)(want < cap ? want : cap);
 }
 
-// q, scale: may both be null (column sums only). colsum: may be null.
-// part_amax / part_sum: [fp8_cols_partials(R, C), C] fp32 workspaces (part_sum
-// only with colsum).
 void launch_fp8_quant_cols_t(const __hip_bfloat16* x, unsigned char* q, float* scale,
                              float* colsum, float* part_amax, float* part_sum, long R, int C,
                              int fmt, hipStream_t stream) {

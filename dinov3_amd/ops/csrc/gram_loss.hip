@@ -50,6 +50,7 @@
 // columns. No float atomics: loss and gradient are bit-identical from run to
 // run and for every panel height.
 
+#include "gram_loss.h"
 #include "mfma.h"
 
 #define GRAM_TILE 128     // rows and columns of an output tile
@@ -300,8 +301,6 @@ void launch_gram_rnorm(const __hip_bfloat16* s, const __hip_bfloat16* t, float* 
   HIP_CHECK_LAUNCH();
 }
 
-// Row tiles tile0 .. tile0 + ntiles - 1 of the G * nT row tiles. P (nullptr:
-// loss only) is [ntiles * 128, nT * 128] bf16; partials is [G * nT, nT] fp32.
 void launch_gram_tiles(const __hip_bfloat16* S, const __hip_bfloat16* T, const float* rs,
                        const float* rt, __hip_bfloat16* P, float* partials, int M, int D, int mode,
                        long tile0, int ntiles, hipStream_t stream) {

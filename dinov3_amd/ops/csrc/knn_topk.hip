@@ -57,6 +57,7 @@
 // conflicts. The staging stores are ds_write_b128 of 8 consecutive lanes to
 // 128 contiguous bytes of one row: 32 distinct banks.
 
+#include "knn_topk.h"
 #include "mfma.h"
 
 typedef bf16x8 knn_bf16x8;
@@ -316,10 +317,6 @@ __global__ __launch_bounds__(KNN_MERGE_THREADS) void merge_kernel(
 
 }  // namespace knn
 
-// Slices of the bank for `splits == 0`: enough blocks for the 256 CUs (one
-// block per CU: the lists and staging buffers take more than half the LDS)
-// when there are few query tiles, one slice once the query tiles fill the
-// device on their own; a slice keeps at least 8 tiles of rows.
 int knn_topk_auto_splits(long Q, long N) {
   const long qtiles = (Q + KNN_TQ - 1) / KNN_TQ;
   if (qtiles >= 256 || qtiles <= 0) return 1;
@@ -330,7 +327,6 @@ int knn_topk_auto_splits(long Q, long N) {
   return s < 1 ? 1 : (int)s;
 }
 
-// ws: [splits, Q, k] 64-bit keys, or nullptr when splits == 1.
 void launch_knn_topk(const __hip_bfloat16* q, const __hip_bfloat16* bank, unsigned long long* ws,
                      float* val, int* idx, long Q, long N, int D, int k, int splits,
                      hipStream_t stream) {

@@ -1,7 +1,7 @@
 // Linear-probe training step, the two non-GEMM parts (docs/KERNELS.md "Linear
 // probe"): softmax cross-entropy over a grid of heads with the gradient written
 // in place, and the SGD-momentum update with the fused bf16 copy of the weights.
-#include "common.h"
+#include "linear_probe.h"
 
 #include <climits>
 
@@ -184,9 +184,6 @@ void probe_ce_kernel(T* __restrict__ logits, const float* __restrict__ bias,
   }
 }
 
-// Row blocks of a launch: every head gets the same number, all heads together
-// stay within PROBE_CE_MAX_BLOCKS (four blocks per CU), and every block runs
-// the same number of row rounds. `row_blocks` > 0 overrides the choice.
 int probe_ce_row_blocks(long B, int G, int row_blocks) {
   const long groups = (B + PROBE_CE_WAVES - 1) / PROBE_CE_WAVES;
   int cap = PROBE_CE_MAX_BLOCKS / G;
@@ -195,14 +192,11 @@ int probe_ce_row_blocks(long B, int G, int row_blocks) {
   return even_row_grid(groups, cap);
 }
 
-// Columns of the workspace / of `out`: dbias [G, Cp] when write_grad, then, from
-// a 4-float boundary on, G losses and G counts.
 void probe_ce_layout(int G, int Cp, bool write_grad, int* ws_cols, int* tail) {
   *tail = write_grad ? G * Cp : 0;
   *ws_cols = *tail + (2 * G + 3) / 4 * 4;
 }
 
-// out [ws_cols] = column sums of the blocks' partial rows; ws holds nblk rows.
 template <typename T>
 void launch_probe_ce(T* logits, const float* bias, const long* labels, float* ws, float* out,
                      long B, int G, int Cp, int C, float grad_scale, bool write_grad, int nblk,

@@ -7,7 +7,7 @@
 // fixed column slice inside a block and leave through the two-stage column
 // reduction of common.h: one partial row per block, no atomics.
 
-#include "common.h"
+#include "norms.h"
 
 #define NORM_BLOCK 256
 // row-grid caps of the backward kernels (one workspace row per block)
@@ -470,8 +470,6 @@ void launch_layernorm_fwd(const T* x, const T* w, const T* b, T* y, float* mean,
                                      rows, D, eps));
 }
 
-// y[r] = LayerNorm(flat[idx[r]]) and sub[r] = flat[idx[r]] in one kernel
-// (D % 8 == 0). Grid and block are those of launch_layernorm_fwd.
 template <typename T>
 void launch_gather_layernorm_fwd(const T* flat, const long* idx, const T* w, const T* b,
                                  T* y, T* sub, float* mean, float* rstd, long rows, int D,
@@ -509,8 +507,6 @@ static int launch_layernorm_bwd_wave(const T* dy, const T* x, const T* w, const 
   return grid;
 }
 
-// dacc[idx[r]] += dx[r] of the LayerNorm backward; wave kernel widths only
-// (D % 8 == 0, D <= 1536 — the caller checks). dw / db / ws as below.
 template <typename T>
 void launch_layernorm_bwd_scatter_acc(const T* dy, const T* x, const T* w, const float* mean,
                                       const float* rstd, T* dacc, const long* idx, float* ws,
@@ -522,8 +518,6 @@ void launch_layernorm_bwd_scatter_acc(const T* dy, const T* x, const T* w, const
   launch_colreduce_finalize<T>(dw_ws, dw, db_ws, db, grid, D, stream);
 }
 
-// dw / db come out in T; `ws` is an fp32 workspace of 2 * COLRED_MAX_PARTIALS
-// rows of D (dgamma partials, then dbeta partials).
 template <typename T>
 void launch_layernorm_bwd(const T* dy, const T* x, const T* w, const float* mean,
                           const float* rstd, T* dx, float* ws, T* dw, T* db, long rows,
@@ -581,7 +575,7 @@ void launch_l2norm_bwd(const T* dy, const T* y, const float* s, T* dx, long rows
                                      eps));
 }
 
-// explicit instantiations used by bindings.cpp
+// explicit instantiations of the launchers declared in norms.h
 #define INSTANTIATE_NORMS(T)                                                              \
   template void launch_layernorm_fwd<T>(const T*, const T*, const T*, T*, float*, float*, \
                                         long, int, float, hipStream_t);                   \

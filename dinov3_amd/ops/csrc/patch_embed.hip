@@ -9,6 +9,7 @@
 // double-purpose staging of the A rows and the W slice per K-step of 32.
 
 #include "mfma.h"
+#include "patch_embed.h"
 
 typedef bf16x8 bf16x8_pe;
 typedef f32x16 f32x16_pe;

@@ -8,7 +8,7 @@
 // 72 ms/step fp32 fallback GEMM + fp32 log_softmax chain measured in the
 // eager path (profiles/, round 1).
 
-#include "common.h"
+#include "proto_ce.h"
 
 #define CE_BLOCK 256
 

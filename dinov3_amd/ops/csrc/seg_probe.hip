@@ -3,7 +3,7 @@
 // logits to the label resolution, per-pixel softmax cross-entropy, the IoU
 // counts, and the gradient folded back to patch resolution, without ever
 // holding the upsampled logits in memory.
-#include "common.h"
+#include "seg_probe.h"
 
 #include <climits>
 
@@ -312,9 +312,6 @@ void seg_sums_finalize_kernel(const float* __restrict__ part_loss,
 int seg_ce_quad_blocks(long quads, int G) { return SegCeTraits::quad_blocks(quads, G); }
 int seg_ce_fin_rows(long cells) { return SegCeTraits::fin_rows(cells) * SegCeTraits::kFinCells; }
 
-// ws [M h w 4 G Cp] and part_db [seg_ce_fin_rows, G Cp] only with write_grad;
-// part_loss [nblk, G], part_area [nblk, G, 3, Cp]; scale (one float on the
-// device, or nullptr) multiplies grad_scale.
 template <typename T>
 void launch_seg_ce(T* logits, const float* bias, const unsigned char* labels, float* ws,
                    float* part_loss, int* part_area, float* part_db, float* loss, long* areas,

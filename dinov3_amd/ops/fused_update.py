@@ -2,7 +2,8 @@
 
 GPU path: one kernel launch walks a packed table of tensor chunks
 (csrc/multi_tensor.hip) — the EMA update over all student shards is a single
-in-place HIP kernel, as required by the north-star. CPU path: torch._foreach.
+in-place HIP kernel, as required by the north-star. The list functions here
+build the table (a MultiTensorPlan) for the one call. CPU path: torch._foreach.
 
 Semantics:
 - EMA: t = m*t + (1-m)*s over matching (teacher, student) leaves
@@ -18,27 +19,29 @@ from typing import List, Optional
 
 import torch
 
+from .mt_plan import MultiTensorPlan, adamw_planned, ema_planned, l2norm_planned
+
 
 def ema_update_(teacher_params: List[torch.Tensor], student_params: List[torch.Tensor], momentum: float) -> None:
+    """t = m t + (1 - m) s in place. Steady-state callers hold a MultiTensorPlan instead."""
     if not teacher_params:
         return
     if teacher_params[0].is_cuda:
-        from . import hip_ops
-
-        hip_ops().multi_tensor_ema(teacher_params, student_params, momentum)
+        ema_planned(MultiTensorPlan([teacher_params, student_params]), momentum)
         return
     torch._foreach_mul_(teacher_params, momentum)
     torch._foreach_add_(teacher_params, student_params, alpha=1.0 - momentum)
 
 
 def grad_l2_norm_sq(grads: List[torch.Tensor]) -> torch.Tensor:
-    """Sum of squares over a list of grads (fp32 scalar on the same device)."""
+    """Sum of squares over a list of grads (fp32 scalar on the same device).
+
+    Steady-state callers hold a MultiTensorPlan instead."""
     if not grads:
         return torch.zeros((), dtype=torch.float32)
     if grads[0].is_cuda:
-        from . import hip_ops
-
-        return hip_ops().multi_tensor_l2norm_sq(grads)
+        sub_id = torch.zeros(len(grads), dtype=torch.int32, device=grads[0].device)
+        return l2norm_planned(MultiTensorPlan([grads]), sub_id, 1)[0]
     return sum(g.float().pow(2).sum() for g in grads)
 
 
@@ -62,19 +65,21 @@ def multi_tensor_adamw_(
     `master` (optional) are fp32 master weights when `params` are bf16; the
     update runs on master and params are re-quantized from it.
     `grad_scale` multiplies grads on the fly (used for clipping).
+    Steady-state callers hold a MultiTensorPlan instead.
     """
     if not params:
         return
+    if params[0].is_cuda:
+        lists = [params, grads, exp_avg, exp_avg_sq] + ([master] if master is not None else [])
+        dev = params[0].device
+        ones = torch.ones(len(params), dtype=torch.float32, device=dev)
+        zeros = torch.zeros(len(params), dtype=torch.float32, device=dev)
+        adamw_planned(MultiTensorPlan(lists), ones, ones, zeros, zeros.int(),
+                      torch.tensor([grad_scale], dtype=torch.float32, device=dev), lr, lr,
+                      weight_decay, beta1, beta2, eps, step, master is not None)
+        return
     bc1 = 1.0 - beta1**step
     bc2 = 1.0 - beta2**step
-    if params[0].is_cuda:
-        from . import hip_ops
-
-        hip_ops().multi_tensor_adamw(
-            params, grads, exp_avg, exp_avg_sq, master if master is not None else [],
-            lr, beta1, beta2, eps, weight_decay, bc1, bc2, grad_scale,
-        )
-        return
     # CPU reference
     work = master if master is not None else params
     gf = [g.float() * grad_scale for g in grads]

@@ -12,7 +12,7 @@ from typing import Sequence
 
 import torch
 
-CHUNK = 65536
+CHUNK = 65536  # elements per chunk; MT_CHUNK of csrc/multi_tensor.h
 
 
 class MultiTensorPlan:
@@ -20,6 +20,10 @@ class MultiTensorPlan:
         self.lists = [list(l) for l in tensor_lists]
         self.n_tensors = len(self.lists[0])
         self.device = self.lists[0][0].device
+        if self.device.type == "cuda":
+            from . import hip_ops
+
+            assert hip_ops().MT_CHUNK == CHUNK, "plan and kernels disagree on the chunk size"
         self.is_bf16 = self.lists[0][0].dtype == torch.bfloat16
         sizes = [t.numel() for t in self.lists[0]]
         ct, co = [], []

@@ -194,45 +194,149 @@ def test_fmha_bwd_matches_reference(ops, N, hd):
 
 
 def test_multi_tensor_ema_gpu(ops):
+    from dinov3_amd.ops import ema_update_
+
     torch.manual_seed(8)
     t = [torch.randn(1000, device=DEV).bfloat16(), torch.randn(3, 7, device=DEV).bfloat16()]
     s = [torch.randn_like(x) for x in t]
     t_ref = [x.float().clone() for x in t]
-    ops.multi_tensor_ema(t, s, 0.9)
+    ema_update_(t, s, 0.9)
     for tr, sv, tv in zip(t_ref, s, t):
         want = 0.9 * tr + 0.1 * sv.float()
         _assert_close(tv, want, atol=0.02, what="ema")
 
 
-def test_multi_tensor_adamw_gpu(ops):
-    torch.manual_seed(9)
-    shapes = [(64, 64), (130,), (1000, 3)]
+def _adamw_step1_ref(p32, g, lr=0.01, wd=0.05, scale=1.0):
+    """fp32 AdamW at step 1 from zero moments: beta = (0.9, 0.999), eps = 1e-8."""
+    gm = g.float() * scale
+    mh = 0.1 * gm / (1 - 0.9)
+    vh = 0.001 * gm * gm / (1 - 0.999)
+    return p32 * (1 - lr * wd) - lr * mh / (vh.sqrt() + 1e-8)
+
+
+def _adamw_state(shapes, grad_dtype=torch.bfloat16):
     p32 = [torch.randn(s, device=DEV) for s in shapes]
     p = [x.bfloat16() for x in p32]
     master = [x.clone() for x in p32]
-    g = [torch.randn(s, device=DEV).bfloat16() for s in shapes]
+    g = [torch.randn(s, device=DEV).to(grad_dtype) for s in shapes]
     m = [torch.zeros(s, device=DEV) for s in shapes]
     v = [torch.zeros(s, device=DEV) for s in shapes]
-    ops.multi_tensor_adamw(p, g, m, v, master, 0.01, 0.9, 0.999, 1e-8, 0.05,
-                           1 - 0.9, 1 - 0.999, 1.0)
+    return p32, p, g, m, v, master
+
+
+def test_multi_tensor_adamw_gpu(ops):
+    from dinov3_amd.ops import multi_tensor_adamw_
+
+    torch.manual_seed(9)
+    shapes = [(64, 64), (130,), (1000, 3)]
+    p32, p, g, m, v, master = _adamw_state(shapes)
+    multi_tensor_adamw_(p, g, m, v, master, 0.01, 0.9, 0.999, 1e-8, 0.05, step=1)
     # torch reference on fp32 copies
     for i, s in enumerate(shapes):
-        ref = p32[i].clone()
-        gm = g[i].float()
-        mm = 0.1 * gm
-        vv = 0.001 * gm * gm
-        mh = mm / (1 - 0.9)
-        vh = vv / (1 - 0.999)
-        ref = ref * (1 - 0.01 * 0.05) - 0.01 * mh / (vh.sqrt() + 1e-8)
+        ref = _adamw_step1_ref(p32[i], g[i])
         _assert_close(master[i], ref, atol=1e-4, what=f"adamw master {i}")
         _assert_close(p[i], ref, atol=0.01, what=f"adamw param {i}")
 
 
 def test_multi_tensor_l2norm_gpu(ops):
+    from dinov3_amd.ops import grad_l2_norm_sq
+
     g = [torch.randn(100, device=DEV).bfloat16(), torch.randn(55, 3, device=DEV).bfloat16()]
-    got = ops.multi_tensor_l2norm_sq(g)
+    got = grad_l2_norm_sq(g)
     want = sum(x.float().pow(2).sum() for x in g)
     _assert_close(got, want, atol=0.5, rtol=1e-2, what="l2norm_sq")
+
+
+def test_multi_tensor_multi_chunk_gpu(ops):
+    """One tensor spans two chunks, the second one ragged, between two small tensors."""
+    from dinov3_amd.ops import ema_update_, grad_l2_norm_sq, multi_tensor_adamw_
+    from dinov3_amd.ops.mt_plan import CHUNK
+
+    assert ops.MT_CHUNK == CHUNK
+    torch.manual_seed(20)
+    shapes = [(3, 7), (CHUNK + 130,), (130,)]
+    t = [torch.randn(s, device=DEV).bfloat16() for s in shapes]
+    s_ = [torch.randn_like(x) for x in t]
+    t_ref = [x.float().clone() for x in t]
+    ema_update_(t, s_, 0.9)
+    for i, (tr, sv, tv) in enumerate(zip(t_ref, s_, t)):
+        _assert_close(tv, 0.9 * tr + 0.1 * sv.float(), atol=0.02, what=f"ema {i}")
+
+    p32, p, g, m, v, master = _adamw_state(shapes)
+    multi_tensor_adamw_(p, g, m, v, master, 0.01, 0.9, 0.999, 1e-8, 0.05, step=1)
+    for i in range(len(shapes)):
+        ref = _adamw_step1_ref(p32[i], g[i])
+        _assert_close(master[i], ref, atol=1e-4, what=f"adamw master {i}")
+        _assert_close(p[i], ref, atol=0.01, what=f"adamw param {i}")
+
+    got = grad_l2_norm_sq(g)
+    want = sum(x.float().pow(2).sum() for x in g)
+    _assert_close(got, want, atol=0.5, rtol=1e-2, what="l2norm_sq")
+
+
+def test_adamw_planned_fp32_grads_gpu(ops):
+    """bf16 params, fp32 grads and fp32 masters: the pairing of the sharded engine."""
+    from dinov3_amd.ops.mt_plan import MultiTensorPlan, adamw_planned
+
+    torch.manual_seed(21)
+    shapes = [(64, 64), (130,), (1000, 3)]
+    p32, p, g, m, v, master = _adamw_state(shapes, grad_dtype=torch.float32)
+    n = len(shapes)
+    ones = torch.ones(n, device=DEV)
+    adamw_planned(MultiTensorPlan([p, g, m, v, master]), ones, ones, torch.zeros(n, device=DEV),
+                  torch.zeros(n, dtype=torch.int32, device=DEV), torch.ones(1, device=DEV),
+                  0.01, 0.01, 0.05, 0.9, 0.999, 1e-8, 1, True)
+    for i in range(n):
+        ref = _adamw_step1_ref(p32[i], g[i])
+        _assert_close(master[i], ref, atol=1e-4, what=f"adamw master {i}")
+        _assert_close(p[i], ref, atol=0.01, what=f"adamw param {i}")
+
+
+def test_adamw_planned_per_tensor_tables_gpu(ops):
+    """Distinct lr multipliers, a frozen last layer, two submodels with their own clip."""
+    from dinov3_amd.ops.mt_plan import MultiTensorPlan, adamw_planned
+
+    torch.manual_seed(22)
+    shapes = [(64, 64), (130,), (1000, 3)]
+    p32, p, g, m, v, master = _adamw_state(shapes)
+    lr_mult, sub_id, clip = [1.0, 0.5, 0.25], [0, 1, 0], [1.0, 0.5]
+    adamw_planned(MultiTensorPlan([p, g, m, v, master]), torch.tensor(lr_mult, device=DEV),
+                  torch.ones(3, device=DEV), torch.tensor([0.0, 0.0, 1.0], device=DEV),
+                  torch.tensor(sub_id, dtype=torch.int32, device=DEV),
+                  torch.tensor(clip, device=DEV), 0.01, 0.0, 0.05, 0.9, 0.999, 1e-8, 1, True)
+    for i in range(2):
+        ref = _adamw_step1_ref(p32[i], g[i], lr=0.01 * lr_mult[i], scale=clip[sub_id[i]])
+        _assert_close(master[i], ref, atol=1e-4, what=f"adamw master {i}")
+        _assert_close(p[i], ref, atol=0.01, what=f"adamw param {i}")
+    # is_last with last_lr = 0: no step and a weight-decay factor of 1
+    assert torch.equal(master[2], p32[2]), "a frozen last layer must not move"
+
+
+def test_l2norm_planned_per_submodel_gpu(ops):
+    from dinov3_amd.ops.mt_plan import MultiTensorPlan, l2norm_planned
+
+    torch.manual_seed(23)
+    g = [torch.randn(s, device=DEV).bfloat16() for s in [(100,), (55, 3), (64, 64)]]
+    sub_id = [0, 1, 0]
+    got = l2norm_planned(MultiTensorPlan([g]), torch.tensor(sub_id, dtype=torch.int32, device=DEV), 2)
+    assert got.shape == (2,)
+    for sub in range(2):
+        want = sum(x.float().pow(2).sum() for x, i in zip(g, sub_id) if i == sub)
+        _assert_close(got[sub], want, atol=0.5, rtol=1e-2, what=f"l2norm submodel {sub}")
+
+
+def test_bindings_check_every_tensor(ops):
+    """A wrong dtype, device or layout raises on the host, before any launch."""
+    x = torch.randn(4, 64, device=DEV).bfloat16()
+    w = torch.ones(64, device=DEV)
+    with pytest.raises(RuntimeError):  # fp32 weight under bf16 activations
+        ops.layernorm_fwd(x, w, w.bfloat16(), 1e-6)
+    with pytest.raises(RuntimeError):  # int32 row index
+        ops.row_gather(x, torch.arange(4, dtype=torch.int32, device=DEV))
+    with pytest.raises(RuntimeError):  # non-contiguous bias
+        ops.bias_gelu_fwd(x, torch.zeros(128, device=DEV).bfloat16()[::2])
+    with pytest.raises(RuntimeError):  # weight on the host
+        ops.layernorm_fwd(x, w.bfloat16().cpu(), w.bfloat16(), 1e-6)
 
 
 def test_ls_axpy_fwd_bwd(ops):
