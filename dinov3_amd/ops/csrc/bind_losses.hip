@@ -11,9 +11,37 @@ using bf16 = __hip_bfloat16;
 
 // ------------------------------ proto CE --------------------------------
 
+// Host checks shared by the prototype ops, before any launch: every tensor is a
+// contiguous HIP tensor of the kernel's dtype (IN_PTR / OUT_PTR), on x's device,
+// and as long as the kernel's indexing assumes.
+void check_len(const torch::Tensor& t, long n, const torch::Tensor& x, const char* who) {
+  TORCH_CHECK(t.defined() && t.numel() == n, who, " must have ", n, " elements, got ",
+              t.defined() ? t.numel() : -1);
+  TORCH_CHECK(t.device() == x.device(), who, " must be on x's device");
+}
+
+// x [S, B, K] student logits and the teacher [T, B, K] (probabilities or logits).
+void check_dino_pair(const torch::Tensor& x, const torch::Tensor& t, const char* op) {
+  TORCH_CHECK(x.dim() == 3 && t.dim() == 3, op, " expects [S,B,K] and [T,B,K]");
+  TORCH_CHECK(t.size(1) == x.size(1) && t.size(2) == x.size(2), op,
+              ": student and teacher must agree in B and K, got ", x.sizes(), " and ", t.sizes());
+  TORCH_CHECK(t.device() == x.device(), op, ": student and teacher must be on one device");
+  TORCH_CHECK(x.size(0) * x.size(1) < (1L << 31) && t.size(0) * t.size(1) < (1L << 31), op,
+              ": too many rows");
+}
+
+// x [M, K] student logits and the row-aligned teacher [M, K].
+void check_ibot_pair(const torch::Tensor& x, const torch::Tensor& t, const char* op) {
+  TORCH_CHECK(x.dim() == 2 && t.dim() == 2, op, " expects [M,K] and [M,K]");
+  TORCH_CHECK(t.sizes() == x.sizes(), op, ": student and teacher must have one shape, got ",
+              x.sizes(), " and ", t.sizes());
+  TORCH_CHECK(t.device() == x.device(), op, ": student and teacher must be on one device");
+  TORCH_CHECK(x.size(0) < (1L << 31), op, ": too many rows");
+}
+
 std::vector<torch::Tensor> dino_ce_fwd(torch::Tensor x, torch::Tensor t, double temp,
                                        bool ignore_diag) {
-  TORCH_CHECK(x.dim() == 3 && t.dim() == 3, "dino_ce expects [S,B,K] and [T,B,K]");
+  check_dino_pair(x, t, "dino_ce_fwd");
   const int S = x.size(0), B = x.size(1);
   const int T = t.size(0);
   const long K = x.size(2);
@@ -29,9 +57,13 @@ std::vector<torch::Tensor> dino_ce_fwd(torch::Tensor x, torch::Tensor t, double 
 torch::Tensor dino_ce_bwd(torch::Tensor g, torch::Tensor x, torch::Tensor t,
                           torch::Tensor lse, torch::Tensor st, double temp,
                           bool ignore_diag) {
+  check_dino_pair(x, t, "dino_ce_bwd");
   const int S = x.size(0), B = x.size(1);
   const int T = t.size(0);
   const long K = x.size(2);
+  check_len(g, 1, x, "dino_ce_bwd: g");
+  check_len(lse, (long)S * B, x, "dino_ce_bwd: lse");
+  check_len(st, (long)S * B, x, "dino_ce_bwd: st");
   auto dx = torch::empty_like(x);
   launch_dino_ce_bwd(IN_PTR(bf16, x), IN_PTR(float, t), IN_PTR(float, lse), IN_PTR(float, st),
                      IN_PTR(float, g), OUT_PTR(bf16, dx), S, T, B, K, (float)(1.0 / temp),
@@ -41,8 +73,10 @@ torch::Tensor dino_ce_bwd(torch::Tensor g, torch::Tensor x, torch::Tensor t,
 
 std::vector<torch::Tensor> ibot_ce_fwd(torch::Tensor x, torch::Tensor t, torch::Tensor w,
                                        double temp) {
+  check_ibot_pair(x, t, "ibot_ce_fwd");
   const int M = x.size(0);
   const long K = x.size(1);
+  check_len(w, M, x, "ibot_ce_fwd: w");
   auto lse = torch::empty({M}, x.options().dtype(torch::kFloat));
   auto st = torch::empty({M}, x.options().dtype(torch::kFloat));
   auto loss = torch::zeros({}, x.options().dtype(torch::kFloat));
@@ -55,8 +89,13 @@ std::vector<torch::Tensor> ibot_ce_fwd(torch::Tensor x, torch::Tensor t, torch::
 torch::Tensor ibot_ce_bwd(torch::Tensor g, torch::Tensor x, torch::Tensor t,
                           torch::Tensor w, torch::Tensor lse, torch::Tensor st,
                           double temp) {
+  check_ibot_pair(x, t, "ibot_ce_bwd");
   const int M = x.size(0);
   const long K = x.size(1);
+  check_len(g, 1, x, "ibot_ce_bwd: g");
+  check_len(w, M, x, "ibot_ce_bwd: w");
+  check_len(lse, M, x, "ibot_ce_bwd: lse");
+  check_len(st, M, x, "ibot_ce_bwd: st");
   auto dx = torch::empty_like(x);
   launch_ibot_ce_bwd(IN_PTR(bf16, x), IN_PTR(float, t), IN_PTR(float, w), IN_PTR(float, lse),
                      IN_PTR(float, st), IN_PTR(float, g), OUT_PTR(bf16, dx), M, K,
@@ -64,18 +103,31 @@ torch::Tensor ibot_ce_bwd(torch::Tensor g, torch::Tensor x, torch::Tensor t,
   return dx;
 }
 
+// A [K] = sum_m exp(x[m, k] / temp) * u[m]; an empty u stands for ones. The
+// kernel loads and stores eight columns at a time: K must be a multiple of 8
+// and x 16-byte aligned. With no rows A is zero, without a launch.
 torch::Tensor sinkhorn_fact_colsum(torch::Tensor x, torch::Tensor u, double temp) {
-  const int M = x.size(0);
+  TORCH_CHECK(x.dim() == 2, "sinkhorn_fact_colsum expects x [M,K]");
   const long K = x.size(1);
+  TORCH_CHECK(x.size(0) < (1L << 31), "sinkhorn_fact_colsum: too many rows");
+  const int M = x.size(0);
+  TORCH_CHECK(K >= 8 && K % 8 == 0,
+              "sinkhorn_fact_colsum: K must be a positive multiple of 8, got ", K);
+  const bf16* x_p = IN_PTR(bf16, x);
+  TORCH_CHECK(is_aligned(x, 16), "sinkhorn_fact_colsum: x must be 16-byte aligned");
+  if (u.defined() && u.numel() > 0) check_len(u, M, x, "sinkhorn_fact_colsum: u");
   auto A = torch::empty({K}, x.options().dtype(torch::kFloat));
-  launch_sinkhorn_fact_colsum(IN_PTR(bf16, x), OPT_IN_PTR(float, u), OUT_PTR(float, A), M, K,
+  launch_sinkhorn_fact_colsum(x_p, OPT_IN_PTR(float, u), OUT_PTR(float, A), M, K,
                               (float)(1.0 / temp), current_stream());
   return A;
 }
 
 torch::Tensor sinkhorn_fact_rowsum(torch::Tensor x, torch::Tensor v, double temp) {
+  TORCH_CHECK(x.dim() == 2, "sinkhorn_fact_rowsum expects x [M,K]");
+  TORCH_CHECK(x.size(0) < (1L << 31), "sinkhorn_fact_rowsum: too many rows");
   const int M = x.size(0);
   const long K = x.size(1);
+  check_len(v, K, x, "sinkhorn_fact_rowsum: v");
   auto u = torch::empty({M}, x.options().dtype(torch::kFloat));
   launch_sinkhorn_fact_rowsum(IN_PTR(bf16, x), IN_PTR(float, v), OUT_PTR(float, u), M, K,
                               (float)(1.0 / temp), current_stream());
@@ -85,8 +137,12 @@ torch::Tensor sinkhorn_fact_rowsum(torch::Tensor x, torch::Tensor v, double temp
 std::vector<torch::Tensor> ibot_ce_fact_fwd(torch::Tensor x, torch::Tensor xt,
                                             torch::Tensor u, torch::Tensor v,
                                             torch::Tensor w, double temp, double tt) {
+  check_ibot_pair(x, xt, "ibot_ce_fact_fwd");
   const int M = x.size(0);
   const long K = x.size(1);
+  check_len(u, M, x, "ibot_ce_fact_fwd: u");
+  check_len(v, K, x, "ibot_ce_fact_fwd: v");
+  check_len(w, M, x, "ibot_ce_fact_fwd: w");
   auto lse = torch::empty({M}, x.options().dtype(torch::kFloat));
   auto st = torch::empty({M}, x.options().dtype(torch::kFloat));
   auto loss = torch::zeros({}, x.options().dtype(torch::kFloat));
@@ -101,8 +157,15 @@ torch::Tensor ibot_ce_fact_bwd(torch::Tensor g, torch::Tensor x, torch::Tensor x
                                torch::Tensor u, torch::Tensor v, torch::Tensor w,
                                torch::Tensor lse, torch::Tensor st, double temp,
                                double tt) {
+  check_ibot_pair(x, xt, "ibot_ce_fact_bwd");
   const int M = x.size(0);
   const long K = x.size(1);
+  check_len(g, 1, x, "ibot_ce_fact_bwd: g");
+  check_len(u, M, x, "ibot_ce_fact_bwd: u");
+  check_len(v, K, x, "ibot_ce_fact_bwd: v");
+  check_len(w, M, x, "ibot_ce_fact_bwd: w");
+  check_len(lse, M, x, "ibot_ce_fact_bwd: lse");
+  check_len(st, M, x, "ibot_ce_fact_bwd: st");
   auto dx = torch::empty_like(x);
   launch_ibot_ce_fact_bwd(IN_PTR(bf16, x), IN_PTR(bf16, xt), IN_PTR(float, u), IN_PTR(float, v),
                           IN_PTR(float, w), IN_PTR(float, lse), IN_PTR(float, st),
@@ -114,9 +177,12 @@ torch::Tensor ibot_ce_fact_bwd(torch::Tensor g, torch::Tensor x, torch::Tensor x
 std::vector<torch::Tensor> dino_ce_fact_fwd(torch::Tensor x, torch::Tensor xt,
                                             torch::Tensor u, torch::Tensor v, double temp,
                                             double tt, bool ignore_diag) {
+  check_dino_pair(x, xt, "dino_ce_fact_fwd");
   const int S = x.size(0), B = x.size(1);
   const int T = xt.size(0);
   const long K = x.size(2);
+  check_len(u, (long)T * B, x, "dino_ce_fact_fwd: u");
+  check_len(v, K, x, "dino_ce_fact_fwd: v");
   auto lse = torch::empty({S * B}, x.options().dtype(torch::kFloat));
   auto st = torch::empty({S * B}, x.options().dtype(torch::kFloat));
   auto loss = torch::zeros({}, x.options().dtype(torch::kFloat));
@@ -131,9 +197,15 @@ torch::Tensor dino_ce_fact_bwd(torch::Tensor g, torch::Tensor x, torch::Tensor x
                                torch::Tensor u, torch::Tensor v, torch::Tensor lse,
                                torch::Tensor st, double temp, double tt,
                                bool ignore_diag) {
+  check_dino_pair(x, xt, "dino_ce_fact_bwd");
   const int S = x.size(0), B = x.size(1);
   const int T = xt.size(0);
   const long K = x.size(2);
+  check_len(g, 1, x, "dino_ce_fact_bwd: g");
+  check_len(u, (long)T * B, x, "dino_ce_fact_bwd: u");
+  check_len(v, K, x, "dino_ce_fact_bwd: v");
+  check_len(lse, (long)S * B, x, "dino_ce_fact_bwd: lse");
+  check_len(st, (long)S * B, x, "dino_ce_fact_bwd: st");
   auto dx = torch::empty_like(x);
   launch_dino_ce_fact_bwd(IN_PTR(bf16, x), IN_PTR(bf16, xt), IN_PTR(float, u), IN_PTR(float, v),
                           IN_PTR(float, lse), IN_PTR(float, st), IN_PTR(float, g),
@@ -151,8 +223,10 @@ std::vector<torch::Tensor> sinkhorn_exp(torch::Tensor x, double temp) {
 }
 
 torch::Tensor sinkhorn_colsum(torch::Tensor Q, torch::Tensor divisor) {
+  TORCH_CHECK(Q.dim() == 2 && Q.size(0) < (1L << 31), "sinkhorn_colsum expects Q [M,K]");
   const int M = Q.size(0);
   const long K = Q.size(1);
+  check_len(divisor, 1, Q, "sinkhorn_colsum: divisor");
   auto out = torch::empty({K}, Q.options());
   launch_sinkhorn_colsum(IN_PTR(float, Q), OUT_PTR(float, out), M, K, IN_PTR(float, divisor),
                          current_stream());
@@ -161,8 +235,11 @@ torch::Tensor sinkhorn_colsum(torch::Tensor Q, torch::Tensor divisor) {
 
 void sinkhorn_div_row(torch::Tensor Q, torch::Tensor col, double k_div, torch::Tensor B,
                       bool scale_back) {
+  TORCH_CHECK(Q.dim() == 2 && Q.size(0) < (1L << 31), "sinkhorn_div_row expects Q [M,K]");
   const int M = Q.size(0);
   const long K = Q.size(1);
+  check_len(col, K, Q, "sinkhorn_div_row: col");
+  check_len(B, 1, Q, "sinkhorn_div_row: B");
   launch_sinkhorn_div_row(OUT_PTR(float, Q), IN_PTR(float, col), M, K, (float)k_div,
                           IN_PTR(float, B), scale_back, current_stream());
 }

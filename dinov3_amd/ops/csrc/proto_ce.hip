@@ -445,6 +445,11 @@ void launch_ibot_ce_bwd(const __hip_bfloat16* x, const float* t, const float* w,
 
 void launch_sinkhorn_fact_colsum(const __hip_bfloat16* x, const float* u, float* A,
                                  int M, long K, float inv_temp, hipStream_t stream) {
+  if (M == 0) {
+    // a rank without rows: A = 0, so the caller's all-reduce still runs on every rank
+    (void)hipMemsetAsync(A, 0, K * sizeof(float), stream);
+    return;
+  }
   const int kw = (int)((K + CE_BLOCK * 8 - 1) / (CE_BLOCK * 8));
   // target >=512 workgroups so the 256-CU chip is filled even at M=128
   int tiles = 512 / (kw > 0 ? kw : 1);
@@ -459,7 +464,8 @@ void launch_sinkhorn_fact_colsum(const __hip_bfloat16* x, const float* u, float*
 
 void launch_sinkhorn_fact_rowsum(const __hip_bfloat16* x, const float* v, float* u,
                                  int M, long K, float inv_temp, hipStream_t stream) {
-  int split = 512 / (M > 0 ? M : 1);
+  if (M == 0) return;
+  int split = 512 / M;
   if (split < 1) split = 1;
   if (split > 16) split = 16;
   if (split > 1) (void)hipMemsetAsync(u, 0, M * sizeof(float), stream);
@@ -510,6 +516,7 @@ void launch_dino_ce_fact_bwd(const __hip_bfloat16* x, const __hip_bfloat16* xt,
 
 void launch_sinkhorn_exp(const __hip_bfloat16* x, float* Q, float* total, long n,
                          float inv_temp, hipStream_t stream) {
+  if (n == 0) return;
   int grid = (int)min((n + CE_BLOCK - 1) / CE_BLOCK, (long)4096);
   hipLaunchKernelGGL(sinkhorn_exp_kernel, dim3(grid), dim3(CE_BLOCK), 0, stream, x, Q,
                      total, n, inv_temp);
@@ -524,6 +531,7 @@ void launch_sinkhorn_colsum(const float* Q, float* out, int M, long K,
 
 void launch_sinkhorn_div_row(float* Q, const float* col, int M, long K, float k_div,
                              const float* B, bool scale_back, hipStream_t stream) {
+  if (M == 0) return;
   hipLaunchKernelGGL(sinkhorn_div_row_kernel, dim3(M), dim3(CE_BLOCK), 0, stream, Q, col,
                      M, K, k_div, B, scale_back);
 }

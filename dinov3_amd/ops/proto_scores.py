@@ -65,6 +65,17 @@ class FactoredProbs:
         return self.materialize()
 
 
+def factored_eligible(teacher_logits: torch.Tensor) -> bool:
+    """True when sinkhorn_knopp_factored can take these logits: bf16 on a HIP
+    device, and — its column-sum kernel loads eight columns at a time — K a
+    multiple of 8 and 16-byte aligned storage. Anything else goes through
+    sinkhorn_knopp."""
+    from . import use_hip
+
+    return (use_hip(teacher_logits) and teacher_logits.dtype == torch.bfloat16
+            and teacher_logits.shape[-1] % 8 == 0 and teacher_logits.data_ptr() % 16 == 0)
+
+
 @torch.no_grad()
 def sinkhorn_knopp_factored(teacher_logits: torch.Tensor, teacher_temp: float,
                             n_iterations: int = 3) -> FactoredProbs:
@@ -273,7 +284,8 @@ def dino_softmax_ce(student_logits: torch.Tensor, teacher_probs: torch.Tensor,
     tp = teacher_probs.float()
     if ignore_diagonal:
         loss_st = -torch.einsum("sbk,tbk->st", logp, tp)
-        loss_st = loss_st - torch.diag_embed(torch.diagonal(loss_st))
+        # zero the s == t pairs; S and T may differ (diag_embed would not broadcast)
+        loss_st = loss_st.masked_fill(torch.eye(S, T, dtype=torch.bool, device=loss_st.device), 0.0)
         M = min(S, T)
         return loss_st.sum() / (B * S * T - B * M)
     return -torch.einsum("sbk,tbk->", logp, tp) / (B * S * T)

@@ -1,4 +1,4 @@
-"""GPU numerics for the fused prototype-CE and sinkhorn kernels."""
+"""GPU numerics for the fused prototype-CE and sinkhorn kernels (elementwise fp64 bounds: test_proto_exact_gpu.py)."""
 
 import pytest
 import torch

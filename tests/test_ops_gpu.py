@@ -339,6 +339,82 @@ def test_bindings_check_every_tensor(ops):
         ops.layernorm_fwd(x, w.bfloat16().cpu(), w.bfloat16(), 1e-6)
 
 
+def _proto_binding_calls(ops):
+    """name -> (function, good arguments) for every prototype-loss binding;
+    tensors by name so that one can be swapped for a malformed one."""
+    S, T, B, M, K = 3, 2, 2, 5, 16
+    f32 = dict(device=DEV, dtype=torch.float32)
+    x3 = torch.zeros(S, B, K, device=DEV).bfloat16()
+    xt3 = torch.zeros(T, B, K, device=DEV).bfloat16()
+    x2 = torch.zeros(M, K, device=DEV).bfloat16()
+    t3, t2 = torch.full((T, B, K), 1.0 / K, **f32), torch.full((M, K), 1.0 / K, **f32)
+    rows3, rows2, uT = torch.ones(S * B, **f32), torch.ones(M, **f32), torch.ones(T * B, **f32)
+    v, g = torch.full((K,), 1.0 / K, **f32), torch.ones((), **f32)
+    return {
+        "dino_ce_fwd": (lambda a: ops.dino_ce_fwd(a["x"], a["t"], 0.1, False), dict(x=x3, t=t3)),
+        "dino_ce_bwd": (lambda a: ops.dino_ce_bwd(a["g"], a["x"], a["t"], a["lse"], a["st"], 0.1, False),
+                        dict(g=g, x=x3, t=t3, lse=rows3, st=rows3)),
+        "ibot_ce_fwd": (lambda a: ops.ibot_ce_fwd(a["x"], a["t"], a["w"], 0.1), dict(x=x2, t=t2, w=rows2)),
+        "ibot_ce_bwd": (lambda a: ops.ibot_ce_bwd(a["g"], a["x"], a["t"], a["w"], a["lse"], a["st"], 0.1),
+                        dict(g=g, x=x2, t=t2, w=rows2, lse=rows2, st=rows2)),
+        "sinkhorn_fact_colsum": (lambda a: ops.sinkhorn_fact_colsum(a["x"], a["u"], 0.1), dict(x=x2, u=rows2)),
+        "sinkhorn_fact_rowsum": (lambda a: ops.sinkhorn_fact_rowsum(a["x"], a["v"], 0.1), dict(x=x2, v=v)),
+        "ibot_ce_fact_fwd": (lambda a: ops.ibot_ce_fact_fwd(a["x"], a["xt"], a["u"], a["v"], a["w"], 0.1, 0.1),
+                             dict(x=x2, xt=x2, u=rows2, v=v, w=rows2)),
+        "ibot_ce_fact_bwd": (lambda a: ops.ibot_ce_fact_bwd(a["g"], a["x"], a["xt"], a["u"], a["v"], a["w"],
+                                                            a["lse"], a["st"], 0.1, 0.1),
+                             dict(g=g, x=x2, xt=x2, u=rows2, v=v, w=rows2, lse=rows2, st=rows2)),
+        "dino_ce_fact_fwd": (lambda a: ops.dino_ce_fact_fwd(a["x"], a["xt"], a["u"], a["v"], 0.1, 0.1, False),
+                             dict(x=x3, xt=xt3, u=uT, v=v)),
+        "dino_ce_fact_bwd": (lambda a: ops.dino_ce_fact_bwd(a["g"], a["x"], a["xt"], a["u"], a["v"], a["lse"],
+                                                            a["st"], 0.1, 0.1, False),
+                             dict(g=g, x=x3, xt=xt3, u=uT, v=v, lse=rows3, st=rows3)),
+        "sinkhorn_exp": (lambda a: ops.sinkhorn_exp(a["x"], 0.1), dict(x=x2)),
+        "sinkhorn_colsum": (lambda a: ops.sinkhorn_colsum(a["Q"], a["divisor"]), dict(Q=t2.clone(), divisor=g)),
+        "sinkhorn_div_row": (lambda a: ops.sinkhorn_div_row(a["Q"], a["col"], float(K), a["B"], True),
+                             dict(Q=t2.clone(), col=v, B=g)),
+    }
+
+
+def test_proto_bindings_check_every_tensor(ops):
+    """Every tensor of every prototype-loss binding: a wrong dtype, a wrong
+    length, a non-contiguous view or a host tensor raises on the host, before
+    any launch; so do a K that is no multiple of 8 and misaligned logits in the
+    vectorised column sum, and a teacher whose B or K differs."""
+    calls = _proto_binding_calls(ops)
+    for name, (fn, good) in calls.items():
+        fn(good)                                           # the well-formed call goes through
+        for key, t in good.items():
+            wrong_dtype = t.double() if t.dtype != torch.float64 else t.float()
+            # one element more, or one column more (one more student row would be a valid input)
+            longer = (torch.cat([t.reshape(-1), t.reshape(-1)[:1]]) if t.dim() <= 1
+                      else torch.cat([t, t[..., :1]], dim=-1))
+            strided = torch.stack([t, t], dim=-1)[..., 0]
+            assert not strided.is_contiguous() or t.numel() <= 1
+            bad = {"dtype": wrong_dtype, "host": t.cpu()}
+            if (name, key) not in (("sinkhorn_exp", "x"), ("sinkhorn_colsum", "Q")):   # any [M, K] is an input there
+                bad["length"] = longer
+            if t.numel() > 1:
+                bad["non-contiguous"] = strided
+            for what, b in bad.items():
+                with pytest.raises(RuntimeError):
+                    fn({**good, key: b})
+                    pytest.fail(f"{name}: {key} with wrong {what} was accepted")
+    torch.cuda.synchronize()
+    x = torch.zeros(5, 20, device=DEV).bfloat16()
+    with pytest.raises(RuntimeError, match="multiple of 8"):
+        ops.sinkhorn_fact_colsum(x, torch.empty(0, device=DEV), 0.1)
+    buf = torch.zeros(5 * 16 + 8, device=DEV).bfloat16()
+    with pytest.raises(RuntimeError, match="aligned"):
+        ops.sinkhorn_fact_colsum(buf[1:81].view(5, 16), torch.empty(0, device=DEV), 0.1)
+    fn, good = calls["dino_ce_fact_fwd"]
+    with pytest.raises(RuntimeError):                      # teacher with another K
+        fn({**good, "xt": torch.zeros(2, 2, 24, device=DEV).bfloat16()})
+    with pytest.raises(RuntimeError):                      # teacher with another B
+        fn({**good, "xt": torch.zeros(2, 3, 16, device=DEV).bfloat16(), "u": torch.ones(6, device=DEV)})
+    torch.cuda.synchronize()
+
+
 def test_ls_axpy_fwd_bwd(ops):
     torch.manual_seed(10)
     R, D = 300, 1024
